@@ -24,6 +24,8 @@ cpu_baseline = the reference's two CPU forms of the block (oracle/lr_cpu_baselin
 SIMD dot product per output) timed on this box's host cores on a bounded sample of the same workload, 5 trials, mean and
 sigma (rank 0, N = 1 only).  verified / max_err = the output of the last timed step checked against the oracle on slabs.
 At N = 1 the line also carries wbfm_chain (configs[2]), channelizer (configs[4]) and fanout (configs[3], degenerate) legs.
+--dump-outputs DIR writes the output of the last timed step (inputs are seeded: the same arguments give the same arrays), so that two builds
+can be compared output for output.
 """
 import argparse
 import json
@@ -37,6 +39,7 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 FP32_PEAK_TFLOPS = 157.3     # MI355X_MICROARCH.md: f32 vector == f32 MFMA peak
+DUMP_BYTES = 48 << 20        # --dump-outputs: what all ranks write together
 
 
 def parse():
@@ -61,6 +64,9 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget (seconds of CPU work)")
     ap.add_argument("--launch-check", action="store_true", help="every rank prints {rank, local_rank, world, gpus} and exits before touching a device: "
                                                                 "the self-launch of --gpus N exercised on a box without GPUs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy in float32 (rank<r>_<name>.npy with N > 1); an output over its share "
+                         "of %d MB is cut to a fixed, seeded sample of rows, whose positions go to DIR/<name>_index.npy in float64" % (DUMP_BYTES >> 20))
     return ap.parse_args()
 
 
@@ -763,6 +769,30 @@ def host_path_report(lr, L, torch, dev):
     return rep
 
 
+def take_outputs(torch, arrays, budget):
+    """--dump-outputs: device copies of {name: 2-D float32 tensor} as the last timed step left them (the spread trials run the step again).  An array
+    larger than its share of `budget` is cut to a fixed sample of rows (numpy default_rng(0), sorted), whose positions go along as <name>_index."""
+    import numpy as np
+    share = budget // max(len(arrays), 1)
+    out = {}
+    for name, t in arrays.items():
+        rows, row_bytes = t.shape[0], t.shape[1] * t.element_size()
+        if rows * row_bytes <= share:
+            out[name] = t.clone()
+            continue
+        idx = np.unique(np.random.default_rng(0).integers(0, rows, share // (row_bytes + 8)))
+        out[name] = t[torch.from_numpy(idx).to(t.device)]
+        out[name + "_index"] = idx.astype(np.float64)
+    return out
+
+
+def write_outputs(path, outs, prefix):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in outs.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), v.cpu().numpy() if hasattr(v, "cpu") else v)
+
+
 def main():
     args = parse()
     self_launch(args)
@@ -826,6 +856,9 @@ def main():
             got = blk.process_device(x.data_ptr(), n, y.data_ptr(), n)
             assert got == n
 
+        def outputs():
+            return {"fir_output": y.view(n, 2)}
+
         out_per_step = n
         alg_bytes = 16.0 * n
         flops = 4.0 * 128 * n if fir_mode == "direct" else 125.0 * n
@@ -851,6 +884,9 @@ def main():
 
         def step():
             produced.append(rx.process_device(x.data_ptr(), n, y.data_ptr(), cap))
+
+        def outputs():
+            return {"wbfm_audio": y[:produced[-1]].view(-1, 1)}
 
         out_per_step = n      # metric counts RF samples in; audio samples out reported in config
         alg_bytes = 8.16 * n
@@ -881,6 +917,9 @@ def main():
             assert rx.chain.start_at(pa) == ps
             produced.append(rx.process_device(x.data_ptr(), n, y.data_ptr(), cap))
 
+        def outputs():
+            return {"timeshard_audio": y[:produced[-1]].view(-1, 1)}
+
         out_per_step = n_total / world      # the job is the recording, whatever the number of ranks
         alg_bytes = 8.16 * (pb - pa)
         flops = 167.0 * (pb - pa)
@@ -910,9 +949,13 @@ def main():
         # double-buffered: the broadcast of slab k+1 (communication stream) overlaps the branch kernels on slab k (FanOut.stream)
         import itertools
         slab_iter = fo.stream(itertools.repeat(x), 2 * n)
+        last = {}
 
         def step():
-            next(slab_iter)
+            last.update(next(slab_iter))
+
+        def outputs():
+            return {"fanout_branch%d" % b: out.view(-1, 2) for b, out in sorted(last.items())}
 
         out_per_step = n
         alg_bytes = 9.6 * n
@@ -940,6 +983,13 @@ def main():
             for _ in range(4):
                 step()
             torch.cuda.synchronize()
+    # the ramp runs as many steps as the clock allows: a chain that carries state from step to step (rotator and decimation phase, filter
+    # histories) starts again here, so that the timed steps compute the same output in every run with the same arguments
+    if args.workload == "wbfm":
+        rx.reset()
+    elif args.workload == "fanout":
+        for br in mine.values():
+            br.block.reset()
     for _ in range(args.warmup):
         step()
     sync_all()
@@ -953,6 +1003,7 @@ def main():
     wall = time.perf_counter() - t0
     ev_ms = L.lrhip_timer_elapsed_ms(timer)
     L.lrhip_timer_destroy(timer)
+    dump = take_outputs(torch, outputs(), DUMP_BYTES // world) if args.dump_outputs else None
     # spread of the GPU figure (benchmarks/luaradio_benchmark.lua:10-13, 722-738: trials, mean and deviation): five more trials of the same K steps, each
     # between its own HIP event pair, AFTER the timed region above (which stays exactly K steps between two barriers) - and in the last of them every step
     # between its own pair, so that a 1-2 % change from one round to the next can be told from the spread of the box
@@ -1027,6 +1078,9 @@ def main():
         torch.cuda.synchronize()
         yard_gbs = 16.0 * n * 5 / (L.lrhip_timer_elapsed_ms(yt) / 1e3) / 1e9
         L.lrhip_timer_destroy(yt)
+
+    if dump is not None:
+        write_outputs(args.dump_outputs, dump, "rank%d_" % rank if world > 1 else "")
 
     if rank == 0:
         total = float(out_per_step) * world * args.steps

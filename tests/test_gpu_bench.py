@@ -41,6 +41,22 @@ def test_timeshard_workload_verifies_its_partition_seams():
     assert d["verified"] is True and d["per_rank_verified"][0]["rms_err_vs_oracle"] <= 1e-5
 
 
+@pytest.mark.parametrize("workload", ["fir", "wbfm"])
+def test_dump_outputs_are_the_same_in_two_runs(workload, tmp_path):
+    """--dump-outputs: seeded inputs, and a stateful chain reset after the clock ramp (whose step count depends on the clock), so two runs with the
+    same arguments write the same arrays - float32 / float64 only, within 64 MB"""
+    args = ["--gpus", "1", "--workload", workload, "--steps", "3", "--warmup", "1", "--log2-samples", "22", "--no-cpu-baseline", "--headline-only"]
+    runs = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        _bench(*args, "--dump-outputs", str(out))
+        runs.append({f.name: np.load(str(f)) for f in sorted(out.iterdir())})
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    assert runs[0] and sorted(runs[0]) == sorted(runs[1])
+    for name, a in runs[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.array_equal(a, runs[1][name]), name
+
+
 def _plain(*args, expect_rc=0):
     """`python bench.py ...` with NO launcher environment: the script has to start its own ranks (radio/core/composite.lua:568-569)"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE", "GROUP_RANK")}

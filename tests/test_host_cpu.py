@@ -205,6 +205,29 @@ def test_bench_recording_is_the_same_whichever_partition_asks():
     assert float(mag.min()) > 0.97 and float(mag.max()) < 1.03          # unit carrier + 1 % noise
 
 
+def test_bench_dump_sample_is_fixed_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: an output over its share of the budget is cut to the same sorted rows in every run, their positions written along
+    in float64; a small one is written whole"""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big, small = torch.arange(200000, dtype=torch.float32).view(-1, 2), torch.ones(10, 1)
+    budget = 1 << 20
+    a = bench.take_outputs(torch, {"big": big, "small": small}, budget)
+    b = bench.take_outputs(torch, {"big": big, "small": small}, budget)
+    assert sorted(a) == ["big", "big_index", "small"] and torch.equal(a["small"], small)
+    idx = a["big_index"]
+    assert idx.dtype == np.float64 and len(idx) > 1000 and np.all(np.diff(idx) > 0) and np.array_equal(idx, b["big_index"])
+    assert torch.equal(a["big"], big[torch.from_numpy(idx.astype(np.int64))])
+    bench.write_outputs(str(tmp_path), a, "")
+    files = sorted(tmp_path.iterdir())
+    assert [f.name for f in files] == ["big.npy", "big_index.npy", "small.npy"]
+    assert sum(f.stat().st_size for f in files) <= budget
+    assert [np.load(str(f)).dtype for f in files] == [np.float32, np.float64, np.float32]
+
+
 def test_fir_mode_table_matches_the_lua_glue():
     """one use_fft table for every front end: luaradio_amd/block.py fir_mode == lrhip.fir_mode in lua/radio/core/lrhip.lua"""
     import re

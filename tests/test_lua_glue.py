@@ -11,11 +11,8 @@ A small Lua tokenizer (comments and strings stripped) holds the glue to
 VERDICT r01 found `b:create_stage()` called but defined nowhere; this test fails on that class of defect.
 """
 import glob
-import importlib.util
 import os
 import re
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LUA_FILES = sorted(glob.glob(os.path.join(ROOT, "lua", "radio", "**", "*.lua"), recursive=True))
@@ -240,195 +237,3 @@ def test_fir_mode_mapping_and_collapse_hook_are_documented():
     assert "function DeviceChainBlock.collapse(connections)" in chain and "return result, chains" in chain
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     assert "collapse(all_connections)" in integ and "chain:initialize()" in integ
-
-
-# ---------------------------------------------------------------------------------------------------------------------------------
-# Load-order model of the binding (VERDICT r02, weak 1): the reference's block files are Lua MODULES whose top-level statements run
-# once, in order; a device variant installed in the middle of a file can be overwritten by a later statement of the same file
-# (radio/blocks/signal/firfilter.lua:400-402 re-assigns process_fft_* after the dot-product ladder of :88-307), and a type signature
-# binds the function VALUE it is given at instantiate() time (radio/core/block.lua:283-288).  tools/apply_lua_binding.py therefore
-# inserts the patch directly above the final `return <Block>`; this test applies it to /root/reference and checks, file by file:
-#   (1) nothing but `return <Block>` executes after the patch (no top-level statement, no assignment to a field of the block);
-#   (2) every function a type signature of the file can bind - add_type_signature's process_func argument, through local aliases,
-#       or `process` by default - is one the patch sets;
-#   (3) the initialize function the signature binds is either replaced by the patch or is host-only in EVERY branch of the
-#       reference file (touches no FFI library) and provides self.out, which the device process() resizes;
-#   (4) the model has teeth: with the patch at the place INTEGRATION.md named in round 2 (first branch of the ladder at :88) it
-#       reports exactly the overwrite the judge found.
-# ---------------------------------------------------------------------------------------------------------------------------------
-REFERENCE = "/root/reference"
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("apply_lua_binding", os.path.join(ROOT, "tools", "apply_lua_binding.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def _depths(code):
-    """[(token, offset, nesting depth BEFORE the token)] for the block-structure keywords and everything else"""
-    out, depth = [], 0
-    for m in re.finditer(r"[A-Za-z_]\w*|\S", code):
-        t = m.group(0)
-        if t in ("end", "until"):
-            depth -= 1
-        out.append((t, m.start(), depth))
-        if t in ("function", "do", "then", "repeat"):
-            depth += 1
-        elif t == "elseif":
-            depth -= 1              # its `then` re-opens the level the `if` opened
-    return out
-
-
-def _function_body(code, start):
-    """text of the function whose `function` keyword is at offset start, up to its matching `end`"""
-    depth = 0
-    for t, off, d in _depths(code[start:]):
-        if t in ("function", "do", "then", "repeat"):
-            depth = d + 1
-        if t in ("end", "until") and d == 0:
-            return code[start: start + off]
-    return code[start:]
-
-
-def _field_assignments(code, var):
-    """[(offset, field)] of `function Var:field(`, `function Var.field(`, `Var.field =` anywhere in the file"""
-    hits = [(m.start(), m.group(1)) for m in re.finditer(r"\bfunction\s+%s[:.](\w+)\s*\(" % re.escape(var), code)]
-    hits += [(m.start(), m.group(1)) for m in re.finditer(r"(?<![\w.])%s\.(\w+)\s*=(?!=)" % re.escape(var), code)]
-    return sorted(hits)
-
-
-def _split_args(code, open_paren):
-    depth, i, args, cur = 0, open_paren, [], []
-    while True:
-        ch = code[i]
-        if ch in "([{":
-            depth += 1
-            if depth > 1:
-                cur.append(ch)
-        elif ch in ")]}":
-            depth -= 1
-            if depth == 0:
-                args.append("".join(cur).strip())
-                return args
-            cur.append(ch)
-        elif ch == "," and depth == 1:
-            args.append("".join(cur).strip())
-            cur = []
-        else:
-            cur.append(ch)
-        i += 1
-
-
-def _bound_functions(code, var):
-    """(process names, initialize names) the file's type signatures can bind"""
-    procs, inits = set(), set()
-
-    def names(expr):
-        if not expr:
-            return None
-        found = set(re.findall(r"\b(?:self|%s)\.(\w+)" % re.escape(var), expr))
-        for ident in re.findall(r"(?<![\w.])([A-Za-z_]\w*)(?![\w.(])", expr):       # local aliases (firfilter.lua:60-62)
-            for m in re.finditer(r"\blocal\s+%s\s*=\s*([^\n]+)" % re.escape(ident), code):
-                found |= set(re.findall(r"\b(?:self|%s)\.(\w+)" % re.escape(var), m.group(1)))
-        return found - {"use_fft"}
-
-    for m in re.finditer(r":add_type_signature\s*\(", code):
-        args = _split_args(code, m.end() - 1)
-        p = names(args[2]) if len(args) > 2 else None
-        i = names(args[3]) if len(args) > 3 else None
-        procs |= p if p else {"process"}
-        inits |= i if i else {"initialize"}
-    return procs, inits
-
-
-def _patch_fields():
-    """{patch name: fields the device variant sets on the block}"""
-    files = load()
-    ew = files[os.path.join("lua", "radio", "blocks", "signal", "elementwise_hip.lua")][0]
-    fields = {}
-    for m in re.finditer(r"\bfunction\s+M\.patch_(\w+)\s*\(\s*(\w+)", ew):
-        name, prm = m.group(1), m.group(2)
-        nxt = re.search(r"\n(?:function\s+M\.|return\s+M)", ew[m.end():])
-        body = ew[m.end(): m.end() + (nxt.start() if nxt else len(ew))]
-        f = set(re.findall(r"\bfunction\s+%s[:.](\w+)" % prm, body)) | set(re.findall(r"\b%s\.(\w+)\s*=(?!=)" % prm, body))
-        if "lrhip.device_block(%s" % prm in body:
-            f.add("create_stage")
-        fields[name] = f
-    fir = files[os.path.join("lua", "radio", "blocks", "signal", "firfilter_hip.lua")][0]
-    fields["firfilter"] = set(re.findall(r"\bfunction\s+FIRFilterBlock[:.](\w+)", fir)) | set(re.findall(r"\bFIRFilterBlock\.(\w+)\s*=(?!=)", fir)) | {"create_stage"}
-    core = files[os.path.join("lua", "radio", "core", "lrhip.lua")][0]
-    unary = set(re.findall(r"(\w+)\s*=\s*true", re.search(r"local unary_ops\s*=\s*\{([^}]*)\}", core).group(1)))
-    binary = set(re.findall(r"(\w+)\s*=\s*true", re.search(r"local binary_ops\s*=\s*\{([^}]*)\}", core).group(1)))
-    for n in unary:
-        fields[n] = fields["unary"]
-    for n in binary:
-        fields[n] = fields["binary"]
-    return fields
-
-
-def _late_assignments(code, var, pos):
-    return sorted({f for off, f in _field_assignments(code, var) if off > pos})
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "radio")), reason="needs the reference checkout (not present on the GPU box)")
-def test_binding_applied_to_the_reference_survives_its_module_load_order():
-    tool = _tool()
-    files = tool.patched_sources(REFERENCE)
-    fields = _patch_fields()
-    assert len(tool.BLOCK_FILES) >= 25
-    for name in tool.BLOCK_FILES:
-        assert name in fields, "no device variant for %s" % name
-        old, new = files[os.path.join("radio", "blocks", "signal", name + ".lua")]
-        code, _ = strip_lua(new)
-        ref_code, _ = strip_lua(old)
-        m = re.search(r"require\(\"\"\)\.patch\(\"\",\s*(\w+)\)", code)          # strings are blanked by strip_lua
-        assert m, name
-        var, pos = m.group(1), m.start()
-        # (1) only `return <Block>` after the patch, at nesting depth 0
-        toks = _depths(code)
-        assert [d for t, off, d in toks if off == pos] == [0], "%s: the patch line is not a top-level statement" % name
-        rest = [t for t, off, d in toks if off >= m.end()]
-        assert rest == ["return", var], (name, rest)
-        assert _late_assignments(code, var, pos) == [], name
-        # (2) everything a type signature can bind is a device function
-        procs, inits = _bound_functions(ref_code, var)
-        assert procs, name
-        missing = procs - fields[name]
-        assert not missing, "%s: type signatures can bind %s, which the device variant does not set" % (name, sorted(missing))
-        # (3) the bound initialize: replaced, or host-only in every branch and providing self.out
-        for ini in inits - fields[name]:
-            bodies = [mm for mm in re.finditer(r"\bfunction\s+%s:%s\s*\(" % (var, ini), ref_code)]
-            assert bodies, (name, ini)
-            for mm in bodies:
-                body = _function_body(ref_code, mm.start())
-                assert not re.search(r"\blib\w+\s*\.", body) and "platform.libs" not in body, "%s:%s() builds library objects the device variant never uses" % (name, ini)
-                assert re.search(r"\bself\.out\s*=", body), "%s:%s() does not provide self.out" % (name, ini)
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "radio")), reason="needs the reference checkout (not present on the GPU box)")
-def test_load_order_model_reports_the_round_2_insertion_point():
-    """the first-branch-of-the-ladder placement (firfilter.lua:88) is overwritten by firfilter.lua:400-402 / :488-490"""
-    text = open(os.path.join(REFERENCE, "radio", "blocks", "signal", "firfilter.lua")).read()
-    marker = "if platform.features.volk then"
-    assert marker in text
-    naive = text.replace(marker, "require('radio.core.lrhip').patch('firfilter', FIRFilterBlock)\n" + marker, 1)
-    code, _ = strip_lua(naive)
-    pos = re.search(r"require\(\"\"\)\.patch\(", code).start()
-    late = _late_assignments(code, "FIRFilterBlock", pos)
-    for f in ("process_fft_complex_input_complex_taps", "process_fft_complex_input_real_taps", "process_fft_real_input_real_taps"):
-        assert f in late, late
-    assert set(late) & _patch_fields()["firfilter"], "the model must flag fields the patch sets"
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "radio")), reason="needs the reference checkout (not present on the GPU box)")
-def test_composite_hook_lands_inside_prepare_to_run():
-    tool = _tool()
-    old, new = tool.patched_sources(REFERENCE)[os.path.join("radio", "core", "composite.lua")]
-    a, b, c2, d = (new.index("function CompositeBlock:_prepare_to_run()"), new.index("require('radio.composites.devicechain').collapse(all_connections)"),
-                   new.index("self:_connect_pipes(all_connections)"), new.index("for _, chain in ipairs(device_chains) do chain:initialize() end"))
-    assert a < new.index("self:_crawl_connections()") < b < c2 < new.index("    self:_initialize()\n", a) < d
-    code, _ = strip_lua(new)
-    toks = re.findall(r"\b\w+\b", code)
-    assert sum(toks.count(k) for k in ("function", "do", "then", "repeat")) - toks.count("elseif") == toks.count("end") + toks.count("until")

@@ -14,8 +14,7 @@
   * inserts the collapse() hooks (devicegraph, devicechain, devicefanout) into CompositeBlock:_prepare_to_run (radio/core/composite.lua:426-470) and the
     parent-side close of the fan-out sockets after the fork loop of CompositeBlock:start (:638-642).
 Without --out the checkout is edited in place; with --out DIR only the touched files are written below DIR (same relative paths).
---diff prints a unified diff instead of writing anything.  tests/test_lua_glue.py runs `patched_sources()` against /root/reference
-(when it is present) and models the load order of every patched file.
+--diff prints a unified diff instead of writing anything.
 """
 import argparse
 import difflib
