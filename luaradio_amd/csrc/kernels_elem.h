@@ -317,16 +317,46 @@ __global__ __launch_bounds__(256) void format_convert_vec_kernel(const RAW *__re
 }
 
 
-// IQFileSink / RealFileSink direction (radio/blocks/sinks/iqfile.lua:68-85, realfile.lua): raw.value = x*scale + offset
+// IQFileSink / RealFileSink direction (radio/blocks/sinks/iqfile.lua:71-94, realfile.lua:70-91): raw.value = x*scale + offset
 // evaluated in double and stored into the raw type by the C conversion LuaJIT applies to a cdata assignment
 // (truncation toward zero for the integer formats), then the byte swap.
+// Two roundings, as in Lua: the product is rounded, then the sum.  The library is built with contraction on, which turns the
+// expression into one v_fma_f64; for u32 (scale 2147483647.5) the product is not exact in double and the single rounding
+// truncates some samples next to an integer differently (x = -0.99999994: Lua 128, fused 127), hence contract(off) here.
+// Out-of-range and NaN samples have no defined result in the reference; the rule (DESIGN.md "File sink records", the same
+// code as lro_format_pack in oracle/lr_oracle.c): 8/16-bit formats and s32 truncate to int32_t saturating at its limits, NaN -> 0,
+// and keep the low bytes; u32 does the same through int64_t; f32 / f64 store the rounded value.
+__device__ __forceinline__ int32_t pack_i32(double v)
+{
+    if (v != v) return 0;
+    if (v >= 2147483648.0) return INT32_MAX;
+    if (v <= -2147483649.0) return INT32_MIN;
+    return (int32_t)v;
+}
+// the low 32 bits of that int64_t, without the backend's f64 -> i64 expansion (whose split step is a v_fmac_f64): t - floor(t / 2^32) * 2^32 is exact
+__device__ __forceinline__ uint32_t pack_u32_low(double v)
+{
+#pragma clang fp contract(off)
+    if (v != v) return 0;
+    if (v >= 9223372036854775808.0) return 0xffffffffu;
+    if (v < -9223372036854775808.0) return 0;
+    const double t = trunc(v);
+    return (uint32_t)(t - ldexp(floor(ldexp(t, -32)), 32));
+}
+
 template <typename RAW, typename VAL, bool SWAP>
 __global__ __launch_bounds__(256) void format_pack_kernel(const float *__restrict__ in, RAW *__restrict__ out, unsigned long n,
                                                           double offset, double scale)
 {
+#pragma clang fp contract(off)
     unsigned long stride = (unsigned long)gridDim.x * blockDim.x;
     for (unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        VAL v = (VAL)((double)in[i] * scale + offset);
+        const double p = (double)in[i] * scale;
+        const double d = p + offset;
+        VAL v;
+        if constexpr (std::is_floating_point<VAL>::value) v = (VAL)d;
+        else if constexpr (std::is_same<VAL, uint32_t>::value) v = pack_u32_low(d);
+        else v = (VAL)pack_i32(d);                      // the low bytes of the int32_t (two's complement)
         RAW r;
         __builtin_memcpy(&r, &v, sizeof(r));
         if (SWAP) r = byteswap_raw(r);

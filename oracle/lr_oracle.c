@@ -645,6 +645,62 @@ long lro_format_convert(const char *format, const unsigned char *raw, long nscal
 }
 
 /* ------------------------------------------------------------------------------------------
+ * IQFileSink / RealFileSink conversion: radio/blocks/sinks/iqfile.lua:71-94, realfile.lua:70-91 with the same formats
+ * table (format_utils.lua:82-97) and swap_bytes (format_utils.lua:105-111):  raw.value = (x*scale) + offset  in Lua
+ * doubles - the product rounded, then the sum rounded (two roundings: LuaJIT does not fuse, and this file is built with
+ * -ffp-contract=off) - stored into the raw type by the cdata assignment (truncation toward zero), then the byte swap.
+ * `nscalars` floats in, nscalars * bytes raw bytes out.  Returns -1 for an unknown format.
+ *
+ * Values the raw integer type cannot hold (|x| > 1, NaN, +-inf) have no defined result in the reference (a C conversion
+ * out of range).  The rule here, shared with format_pack_kernel (luaradio_amd/csrc/kernels_elem.h) and stated in
+ * DESIGN.md ("File sink records"):
+ *   8/16-bit formats and s32: truncate to int32_t, saturating at INT32_MIN / INT32_MAX, NaN -> 0; keep the low bytes
+ *   u32:                      truncate to int64_t, saturating at INT64_MIN / INT64_MAX, NaN -> 0; keep the low 4 bytes
+ *   f32 / f64:                the rounded value itself (-0.0 becomes +0.0 through the + 0 of the formula)
+ * ---------------------------------------------------------------------------------------- */
+static int32_t lro_pack_i32(double v)
+{
+    if (v != v) return 0;
+    if (v >= 2147483648.0) return INT32_MAX;
+    if (v <= -2147483649.0) return INT32_MIN;
+    return (int32_t)v;
+}
+static int64_t lro_pack_i64(double v)
+{
+    if (v != v) return 0;
+    if (v >= 9223372036854775808.0) return INT64_MAX;
+    if (v < -9223372036854775808.0) return INT64_MIN;
+    return (int64_t)v;
+}
+
+long lro_format_pack(const char *format, const float *in, long nscalars, unsigned char *raw)
+{
+    static const struct { const char *name; int bytes, cls, be; double offset, scale; } F[] = {
+        {"u8", 1, 0, 0, 127.5, 127.5}, {"s8", 1, 1, 0, 0, 127.5},
+        {"u16le", 2, 2, 0, 32767.5, 32767.5}, {"u16be", 2, 2, 1, 32767.5, 32767.5},
+        {"s16le", 2, 3, 0, 0, 32767.5}, {"s16be", 2, 3, 1, 0, 32767.5},
+        {"u32le", 4, 4, 0, 2147483647.5, 2147483647.5}, {"u32be", 4, 4, 1, 2147483647.5, 2147483647.5},
+        {"s32le", 4, 5, 0, 0, 2147483647.5}, {"s32be", 4, 5, 1, 0, 2147483647.5},
+        {"f32le", 4, 6, 0, 0, 1.0}, {"f32be", 4, 6, 1, 0, 1.0}, {"f64le", 8, 7, 0, 0, 1.0}, {"f64be", 8, 7, 1, 0, 1.0}};
+    int k = -1;
+    for (unsigned i = 0; i < sizeof(F) / sizeof(F[0]); i++) if (!strcmp(F[i].name, format)) k = (int)i;
+    if (k < 0) return -1;
+    for (long i = 0; i < nscalars; i++) {
+        double p = (double)in[i] * F[k].scale;       /* iqfile.lua:77-78, realfile.lua:76: x*scale, rounded */
+        double v = p + F[k].offset;                  /* + offset, rounded */
+        unsigned char b[8];
+        switch (F[k].cls) {
+            case 4: { uint32_t t = (uint32_t)(uint64_t)lro_pack_i64(v); memcpy(b, &t, 4); break; }
+            case 6: { float t = (float)v; memcpy(b, &t, 4); break; }
+            case 7: memcpy(b, &v, 8); break;
+            default: { int32_t t = lro_pack_i32(v); memcpy(b, &t, 4); break; }     /* host is little-endian: the low bytes first */
+        }
+        for (int j = 0; j < F[k].bytes; j++) raw[i * F[k].bytes + j] = b[F[k].be ? F[k].bytes - 1 - j : j];
+    }
+    return nscalars;
+}
+
+/* ------------------------------------------------------------------------------------------
  * FrequencyModulatorBlock: radio/blocks/signal/frequencymodulator.lua:71-90 (pure-Lua branch):
  * phase (a Lua double) = (phase + delta*x) % (2 pi); out = (cosf(phase), sinf(phase)) - the double is narrowed to
  * float at the cosf/sinf call (ffi.C.cosf takes a float).  Lua's % is a floored modulo.

@@ -92,6 +92,8 @@ def lib():
         L.lro_multiply_conjugate.argtypes = [fp, fp, C.c_long, fp]
         L.lro_format_convert.restype = C.c_long
         L.lro_format_convert.argtypes = [C.c_char_p, C.c_char_p, C.c_long, fp]
+        L.lro_format_pack.restype = C.c_long
+        L.lro_format_pack.argtypes = [C.c_char_p, fp, C.c_long, C.c_char_p]
         _lib = L
     return _lib
 
@@ -472,6 +474,22 @@ def format_convert(fmt, raw, complex_out):
     if n < 0:
         raise ValueError('Unsupported format ("%s")' % fmt)
     return out.view(np.complex64) if complex_out else out
+
+
+def format_pack(fmt, x):
+    """IQFileSink / RealFileSink conversion of samples to raw file bytes (iqfile.lua:71-94, realfile.lua:70-91): two roundings,
+    truncation, byte swap; out-of-range and NaN samples by the rule stated at lro_format_pack ("File sink records").
+    x: ComplexFloat32 (interleaved I/Q records) or Float32 samples.  Returns bytes."""
+    x = np.ascontiguousarray(x)
+    xf = x.view(np.float32) if np.iscomplexobj(x) else x.astype(np.float32, copy=False)
+    xf = np.ascontiguousarray(xf)
+    if fmt not in FORMAT_BYTES:
+        raise ValueError('Unsupported format ("%s")' % fmt)
+    raw = C.create_string_buffer(len(xf) * FORMAT_BYTES[fmt])
+    n = lib().lro_format_pack(fmt.encode(), _fp(xf), len(xf), raw)
+    if n < 0:
+        raise ValueError('Unsupported format ("%s")' % fmt)
+    return raw.raw
 
 
 # ---------------------------------------------------------------- composites (composition of the pinned blocks)

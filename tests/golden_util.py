@@ -60,3 +60,21 @@ def run_whole_and_samplewise(make_block, x):
     parts = [p for p in parts if len(p)]
     samplewise = np.concatenate(parts) if parts else whole[:0]
     return whole, samplewise
+
+
+def pack_edge_values():
+    """Float32 samples at the edges of the file-sink record conversion (lro_format_pack / format_pack_kernel): exact +-1 and 0, -0.0,
+    one ulp inside +-1, subnormals, |x| in (1, 4], magnitudes past every integer type's range, NaN and +-inf"""
+    sub = np.array([1, 2, 0x7fffff, 0x400000], np.uint32).view(np.float32)
+    e = [0.0, -0.0, 1.0, -1.0, 0.5, -0.5, 1 - 2.0 ** -24, -1 + 2.0 ** -24, 2.0 ** -24, -2.0 ** -24, 1 / 127.5, -1 / 127.5,
+         1.0000001, -1.0000001, 1.5, -1.5, 2.0, -2.0, 3.999, -3.999, 4.0, -4.0, 255.0, -255.0, 1e3, -1e3, 65536.5, -65536.5,
+         2.0 ** 31, -2.0 ** 31, 2.0 ** 32, 1e10, -1e10, 2.0 ** 62, 2.0 ** 63, -2.0 ** 63, 2.0 ** 64, 3.4e38, -3.4e38,
+         np.nan, np.inf, -np.inf]
+    return np.concatenate([np.array(e, np.float32), sub, -sub])
+
+
+def u32_pack_straddle():
+    """tests/golden/u32_pack_straddle.json: the float32 inputs in [-1, 1] whose u32 record differs between two roundings and one"""
+    with open(os.path.join(GOLDEN_DIR, "u32_pack_straddle.json")) as f:
+        doc = json.load(f)
+    return np.array([int(b, 16) for b in doc["bits"]], np.uint32).view(np.float32), doc["two_roundings"], doc["one_rounding"]

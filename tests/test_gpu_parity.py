@@ -2037,6 +2037,119 @@ def test_file_sinks_round_trip_and_truncation(cplx):
     assert np.array_equal(np.frombuffer(buf.getvalue(), "<i2"), np.trunc(flat.astype(np.float64) * 32767.5).astype(np.int16))
 
 
+PACK_LENGTHS = [1, 2, 3, 5, 1023, 1025, 300003, (1 << 19) + 7, (1 << 22) + 3]      # ragged tails; 2^19 and more: the host piece pipeline (chain.h)
+
+
+@pytest.fixture(scope="module")
+def pack_pool():
+    return np.random.default_rng(31).uniform(-1, 1, 2 * PACK_LENGTHS[-1]).astype(np.float32)
+
+
+def _pack_input(pool, n, cplx):
+    """n samples: uniform in [-1, 1] with the edge values (golden_util.pack_edge_values) and the u32 straddle inputs
+    (golden/u32_pack_straddle.json) written over the head, the middle and the ragged tail"""
+    ns = n * (2 if cplx else 1)
+    f = pool[:ns].copy()
+    edges = np.concatenate([G.pack_edge_values(), G.u32_pack_straddle()[0]])
+    k = len(edges)
+    for at in ((0, ns // 2 - k // 2, ns - k) if ns >= 3 * k else (0,)):
+        m = min(k, ns - at)
+        f[at:at + m] = edges[:m]
+    return f.view(np.complex64) if cplx else f
+
+
+def _assert_same_records(got, want, fmt, x):
+    nb = O.FORMAT_BYTES[fmt]
+    assert len(got) == len(want), (fmt, len(got), len(want))
+    if got != want:
+        g, w = np.frombuffer(got, np.uint8).reshape(-1, nb), np.frombuffer(want, np.uint8).reshape(-1, nb)
+        bad = np.flatnonzero(np.any(g != w, axis=1))
+        flat = x.view(np.float32) if np.iscomplexobj(x) else x
+        raise AssertionError("%s: %d records differ, first at scalar %d (x = %r): device %s, oracle %s"
+                             % (fmt, len(bad), bad[0], float(flat[bad[0]]), g[bad[0]].tobytes().hex(), w[bad[0]].tobytes().hex()))
+
+
+def _sink_bytes(fmt, cplx, parts):
+    import io
+    buf = io.BytesIO()
+    snk = (lr.IQFileSink if cplx else lr.RealFileSink)(buf, fmt)
+    snk.differentiate([types.ComplexFloat32 if cplx else types.Float32])
+    snk.initialize()
+    for p in parts:
+        snk.process(p)
+    snk.cleanup()
+    return buf.getvalue()
+
+
+@pytest.mark.parametrize("cplx", [True, False])
+@pytest.mark.parametrize("fmt", list(O.FORMAT_BYTES))
+def test_file_sink_pack_bit_exact(pack_pool, fmt, cplx):
+    """format_pack_kernel (IQFileSink / RealFileSink records) byte for byte against O.format_pack: every length of PACK_LENGTHS, with
+    in-range samples, exact +-1 / 0 / -0.0, subnormals, |x| in (1, 4], huge magnitudes, NaN / +-inf and the u32 inputs on which a fused
+    x*scale + offset truncates differently from the reference's two roundings; one ragged chunking of one sink"""
+    for n in PACK_LENGTHS:
+        x = _pack_input(pack_pool, n, cplx)
+        _assert_same_records(_sink_bytes(fmt, cplx, [x]), O.format_pack(fmt, x), fmt, x)
+    x = _pack_input(pack_pool, 300003, cplx)
+    cuts = [0, 1, 4, 1000, 65537, 200000, 300003]
+    _assert_same_records(_sink_bytes(fmt, cplx, [x[a:b] for a, b in zip(cuts, cuts[1:])]), O.format_pack(fmt, x), fmt, x)
+    if fmt.startswith("u32"):
+        s, two, _ = G.u32_pack_straddle()
+        xs = (s.astype(np.complex64) if cplx else s)
+        got = np.frombuffer(_sink_bytes(fmt, cplx, [xs]), ">u4" if fmt.endswith("be") else "<u4")
+        assert got[::2 if cplx else 1].tolist() == two, (fmt, got)
+
+
+def _chain_records(blocks, parts, record_size):
+    """a chain whose last stage is a file sink's pack stage: lrhip_chain_execute hands out raw records (record_size bytes per sample)"""
+    import ctypes as C
+    from luaradio_amd import _lib
+    L = _lib.load()
+    arr = (C.c_void_p * len(blocks))(*[b.stage_handle() for b in blocks])
+    c = _lib.check_ptr(L.lrhip_chain_create_ex(arr, len(blocks), _lib.CHAIN_EXACT), "Creating lrhip chain object")
+    out = []
+    try:
+        for p in parts:
+            p = np.ascontiguousarray(p)
+            cap = L.lrhip_chain_max_output(c, len(p))
+            buf = np.empty(max(cap, 1) * record_size, np.uint8)
+            n = _lib.check(L.lrhip_chain_execute(c, p.ctypes.data_as(C.c_void_p), len(p), buf.ctypes.data_as(C.c_void_p), cap), "chain:process")
+            out.append(buf[:n * record_size].tobytes())
+    finally:
+        L.lrhip_chain_destroy(c)
+    return b"".join(out)
+
+
+@pytest.mark.parametrize("tail", ["s16le", "u8"])
+def test_file_sink_pack_at_the_tail_of_a_chain(tail):
+    """translator -> lowpass -> downsampler -> IQFileSink('s16le'), and the same front end -> discriminator -> RealFileSink('u8'): the records a
+    chain ending in the pack stage hands out equal the pack (oracle and stand-alone sink) of the same chain's Float32 output, ragged chunks.
+    The input is scaled past full scale and the discriminator output spans +-5, so both tails see out-of-range samples too."""
+    rate = 1e6
+    rng = np.random.default_rng(41)
+    x = (1.5 * rand_c(rng, (1 << 20) + 5)).astype(np.complex64)
+    cuts = [0, 1, 7, 4096, 70001, 333333, 900000, len(x)]
+    parts = [x[a:b] for a, b in zip(cuts, cuts[1:])]
+    cplx = tail == "s16le"
+
+    def front():
+        blks = [make(lr.FrequencyTranslatorBlock, [0.2e6], x, rate=rate), make(lr.LowpassFilterBlock, [64, 0.1e6], x, rate=rate),
+                make(lr.DownsamplerBlock, [4], x, rate=rate)]
+        if not cplx:
+            blks.append(make(lr.FrequencyDiscriminatorBlock, [0.1], x, rate=rate / 4))     # out = arg / (2 pi 0.1): up to +-5
+        return blks
+
+    floats = lr.Chain(front(), exact=True)
+    y = np.concatenate([floats.process(p) for p in parts])
+    assert len(y) == (len(x) + 3) // 4
+    snk = make(lr.IQFileSink if cplx else lr.RealFileSink, [__import__("io").BytesIO(), tail], y, rate=rate / 4)
+    got = _chain_records(front() + [snk], parts, snk.record_size)
+    _assert_same_records(got, O.format_pack(tail, y), tail, y)
+    assert got == _sink_bytes(tail, cplx, [y])
+    flat = y.view(np.float32) if cplx else y
+    assert np.any(np.abs(flat) > 1) and np.any(np.abs(flat) < 1)
+
+
 def test_chain_reset_restores_the_initial_state():
     """lrhip_chain_reset(): every stage of the chain, including the fused copies the chain built itself, starts over"""
     rng = np.random.default_rng(17)

@@ -294,3 +294,112 @@ def test_timed_cpu_baseline_forms_match_golden_and_f64():
     ct = (O.firwin_lowpass(64, 0.3) * (1 + 0.5j)).astype(np.complex64)
     x = (rng.uniform(-1, 1, 9000) + 1j * rng.uniform(-1, 1, 9000)).astype(np.complex64)
     assert G.max_abs_err(O.baseline_fir_overlap_save(ct, x), O.FIR(ct, True, O.MODE_F64).process(x)) < 1e-6
+
+
+# ---------------------------------------------------------------- IQFileSink / RealFileSink records (lro_format_pack)
+SINK_EPS = {"u8": 1e-1, "s8": 1e-1, "u16le": 1e-4, "u16be": 1e-4, "s16le": 1e-4, "s16be": 1e-4, "u32le": 1e-6, "u32be": 1e-6,
+            "s32le": 1e-6, "s32be": 1e-6, "f32le": 1e-6, "f32be": 1e-6, "f64le": 1e-6, "f64be": 1e-6}     # tests/blocks/sinks/iqfile_spec.lua
+PACK_PARAMS = {"u8": (127.5, 127.5), "s8": (0.0, 127.5), "u16": (32767.5, 32767.5), "s16": (0.0, 32767.5),
+               "u32": (2147483647.5, 2147483647.5), "s32": (0.0, 2147483647.5), "f32": (0.0, 1.0), "f64": (0.0, 1.0)}
+
+
+def _pack_numpy(fmt, xf):
+    """a second, independent restatement of the sink records (numpy float64 arithmetic does not fuse: two roundings) with the
+    out-of-range rule of DESIGN.md "File sink records" written on saturating clips instead of comparisons"""
+    kind, end = fmt[:-2] if fmt.endswith(("le", "be")) else fmt, ">" if fmt.endswith("be") else "<"
+    offset, scale = PACK_PARAMS[kind]
+    d = xf.astype(np.float64) * scale + offset
+    if kind in ("f32", "f64"):
+        return d.astype(end + "f" + str(int(kind[1:]) // 8)).tobytes()
+    t = np.trunc(np.where(np.isnan(d), 0.0, d))
+    if kind == "u32":
+        low = np.where(t >= 2.0 ** 63, 2.0 ** 32 - 1, np.where(t < -2.0 ** 63, 0.0, np.mod(np.clip(t, -2.0 ** 63, 2.0 ** 63), 2.0 ** 32)))
+        return low.astype(np.uint64).astype(end + "u4").tobytes()
+    i32 = np.clip(t, -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int64)
+    nbytes = O.FORMAT_BYTES[fmt]
+    return (i32 & ((1 << (8 * nbytes)) - 1)).astype(end + "u" + str(nbytes)).tobytes()
+
+
+def test_file_sink_pack_round_trip_spec_epsilons():
+    """iqfile_spec.lua / realfile_spec.lua (sinks): a 256-sample vector written in every format and read back by the source conversion
+    is within the reference's per-format epsilon; the float formats reproduce it exactly"""
+    rng = np.random.default_rng(5)
+    for cplx in (True, False):
+        x = (rng.uniform(-1, 1, 256) + 1j * rng.uniform(-1, 1, 256)).astype(np.complex64) if cplx else rng.uniform(-1, 1, 256).astype(np.float32)
+        for fmt, eps in SINK_EPS.items():
+            raw = O.format_pack(fmt, x)
+            assert len(raw) == O.FORMAT_BYTES[fmt] * 256 * (2 if cplx else 1)
+            back = O.format_convert(fmt, raw, cplx)
+            assert G.max_abs_err(back, x) < eps, fmt
+            if fmt[0] == "f":
+                assert np.array_equal(back, x), fmt
+
+
+def test_file_sink_pack_hand_derived_records():
+    """records worked out by hand from format_utils.lua:82-97 and the out-of-range rule; every big-endian format is the byte reverse of its le twin"""
+    P = lambda fmt, *v: O.format_pack(fmt, np.array(v, np.float32))
+    assert P("u8", 1, -1, 0) == bytes([255, 0, 127])                   # 255.0, 0.0, 127.5 -> 127
+    assert P("s8", 1, -1, 0, 0.5) == bytes([127, 129, 0, 63])          # 127.5 -> 127, -127.5 -> -127, 63.75 -> 63
+    assert np.array_equal(np.frombuffer(P("s16le", 1, -1, 0), "<i2"), [32767, -32767, 0])
+    assert np.array_equal(np.frombuffer(P("u16le", 1, -1, 0), "<u2"), [65535, 0, 32767])
+    assert np.array_equal(np.frombuffer(P("u32le", 1, -1, 0), "<u4"), [4294967295, 0, 2147483647])
+    assert np.array_equal(np.frombuffer(P("s32le", 1, -1, 0), "<i4"), [2147483647, -2147483647, 0])
+    assert P("f32le", -0.0) == np.float32(0.0).tobytes() and P("f64le", -0.0) == np.float64(0.0).tobytes()   # -0.0*1 + 0 = +0.0
+    # the out-of-range rule: int32 saturating truncation (NaN -> 0), low bytes; u32 through int64
+    assert P("u8", 1.5, -1.5, np.nan, np.inf, -np.inf) == bytes([318 & 255, -63 & 255, 0, 255, 0])
+    assert np.array_equal(np.frombuffer(P("s16le", 1.5, 1e6, -1e6, np.nan), "<u2"), [49151 & 0xffff, 0xffff, 0, 0])
+    assert np.array_equal(np.frombuffer(P("s32le", 1.5, -1.5, np.nan, np.inf, -np.inf), "<i4"), [2147483647, -2147483648, 0, 2147483647, -2147483648])
+    assert np.array_equal(np.frombuffer(P("u32le", 1.5, -1.5, 3e38, -3e38, np.nan), "<u4"),
+                          [5368709118 & 0xffffffff, -1073741823 & 0xffffffff, 0xffffffff, 0, 0])
+    x = np.concatenate([np.random.default_rng(6).uniform(-1, 1, 1000).astype(np.float32), G.pack_edge_values()])
+    for le in [f for f in O.FORMAT_BYTES if f.endswith("le")]:
+        be, nb = le[:-2] + "be", O.FORMAT_BYTES[le]
+        a = np.frombuffer(O.format_pack(le, x), np.uint8).reshape(-1, nb)
+        assert O.format_pack(be, x) == a[:, ::-1].tobytes(), be
+    assert O.format_pack("f32le", x) == np.where(x == 0, np.float32(0), x).astype("<f4").tobytes()
+
+
+def test_file_sink_pack_matches_numpy_restatement():
+    """lro_format_pack against an independent numpy restatement, every format, in-range samples and every edge of the rule"""
+    rng = np.random.default_rng(7)
+    x = np.concatenate([rng.uniform(-1, 1, 20000), rng.uniform(-4, 4, 5000), rng.standard_normal(5000) * 1e12]).astype(np.float32)
+    x = np.concatenate([x, G.pack_edge_values()])
+    with np.errstate(invalid="ignore"):
+        for fmt in O.FORMAT_BYTES:
+            assert O.format_pack(fmt, x) == _pack_numpy(fmt, x), fmt
+    with pytest.raises(ValueError):
+        O.format_pack("u24le", x)
+
+
+def test_u32_pack_straddle_exhaustive_search():
+    """every float32 in [-1, 1], both signs, every binade: the u32 records for which the reference's two roundings and one (fused) rounding
+    truncate to different integers.  Two roundings: numpy float64 (no contraction).  One rounding: the exact rational value rounded once
+    (Fraction -> float is correctly rounded), checked on every candidate whose two-rounding value lies within 2^-19 of an integer - both
+    values lie within 2^-20 + 2^-21 of the exact one below 2^32, so no other input can truncate differently.  The hits are the fixture
+    tests/golden/u32_pack_straddle.json (used by the GPU test), and the oracle writes the two-rounding answer for each."""
+    import math
+    from fractions import Fraction
+    S = 2 ** 32 - 1
+    sc = np.float64(S / 2)
+    hits, ncand, top, chunk = [], 0, 0x3f800000, 1 << 24          # 0x3f800000: the bits of 1.0f
+    for sign in (0, 0x80000000):
+        for a in range(0, top + 1, chunk):
+            b = np.arange(a, min(a + chunk, top + 1), dtype=np.uint32) | np.uint32(sign)
+            s2 = b.view(np.float32).astype(np.float64)
+            s2 *= sc
+            s2 += sc
+            c = np.abs(s2 - np.rint(s2)) <= 2.0 ** -19
+            for bits, sv in zip(b[c].tolist(), s2[c].tolist()):
+                ncand += 1
+                xv = float(np.uint32(bits).view(np.float32))
+                one = float(Fraction(xv) * Fraction(S, 2) + Fraction(S, 2))
+                if math.trunc(one) != math.trunc(sv):
+                    hits.append((bits, math.trunc(sv), math.trunc(one)))
+    assert ncand > 1000                                               # the filter did look at the near-integer values
+    fx, two, one = G.u32_pack_straddle()
+    assert hits == list(zip(fx.view(np.uint32).tolist(), two, one))
+    x = np.array([h[0] for h in hits], np.uint32).view(np.float32)
+    assert set(x.tolist()) >= {float(np.float32(v)) for v in (-0.99999994, -0.9999999, -0.9999998, -0.99999976)}
+    got = np.frombuffer(O.format_pack("u32le", x), "<u4")
+    assert got.tolist() == [h[1] for h in hits] and all(h[1] != h[2] for h in hits)
+    assert O.format_pack("u32be", x) == got.astype(">u4").tobytes()
