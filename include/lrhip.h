@@ -111,6 +111,9 @@ lrhip_stage_t *lrhip_format_pack_create(const char *format, int complex_in);
  * (multiplyconjugate.lua:41-59, complex only), "add" (add.lua), "subtract" (subtract.lua), "floattocomplex" (floattocomplex.lua: two Float32 inputs ->
  * ComplexFloat32 (in1, in2); input_complex ignored).  Replaces
  * volk_32fc_x2_multiply_32fc_a / volk_32f_x2_multiply_32f_a / volk_32fc_x2_multiply_conjugate_32fc_a.
+ * op = "sampler" (radio/blocks/signal/sampler.lua:33-53): in1 = data (ComplexFloat32 if input_complex, else Float32), in2 = a Float32
+ * clock (4 B whatever the data type); emits data[i] where clock[i] > 0 and the last clock sample != 0 before it was < 0 (initial state LOW).
+ * The output count depends on the clock: at most ceil(n/2) + 1 = lrhip_stage_max_output(); the call returns the exact count.
  * Executed with lrhip_stage_execute2*(). */
 lrhip_stage_t *lrhip_binary_create(const char *op, int input_complex);
 
@@ -135,7 +138,18 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
 /* One-input element-wise blocks. op: "complexmagnitude", "complexphase", "complextoreal", "complextoimag",
  * "complexconjugate" (ComplexFloat32 in), "realtocomplex", "absolutevalue" (Float32 in), and "addconstant"
  * (radio/blocks/signal/addconstant.lua:26-75: constant (re, im); constant_complex / input_complex as for
- * lrhip_multiply_constant_create).  For the ops with a fixed input type input_complex is ignored. */
+ * lrhip_multiply_constant_create).  For the ops with a fixed input type input_complex is ignored.
+ * The blocks between a filtered baseband and a bit stream carry double parameters in the op string, "name:key=value:key=value"
+ * (values as %.17g / repr(float), parsed with strtod; re / im / constant_complex / input_complex ignored; a malformed string, a missing or
+ * unknown key returns NULL with an lrhip_strerror() message).  All exact (compared with ==), state carried across calls:
+ *   "zerocrossingclockrecovery:period=P:threshold=T"  (zerocrossingclockrecovery.lua:35-73, P = rate / baudrate) Float32 -> +-1 Float32
+ *   "slicer:threshold=T"                               (slicer.lua) Float32 -> Bit (1 B): x > T in double
+ *   "differentialdecoder:invert=0|1"                   (differentialdecoder.lua) Bit -> Bit: prev ^ x, or (prev ^ x + 1) % 2; prev = last input byte
+ *   "clocksampler:period=P:threshold=T"                sampler(data = x, clock = zerocrossingclockrecovery(x)) as one stage, Float32 -> Float32,
+ *                                                      count data-dependent (<= ceil(n/2) + 1).  In a chain a slicer [and a differentialdecoder]
+ *                                                      right after it run in its final pass (Bit out), except with LRHIP_CHAIN_NO_FUSION;
+ *                                                      the fused stage continues the carried state of the caller's clocksampler and decoder.
+ * The sampler and the clocksampler have memory() -1: chains holding them refuse time partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */
 lrhip_stage_t *lrhip_delay_create(unsigned num_samples, int elem_size);
@@ -175,7 +189,9 @@ unsigned long lrhip_stage_max_output(const lrhip_stage_t *q, unsigned long n_in)
 long lrhip_stage_execute(lrhip_stage_t *q, const void *in_host, unsigned long n_in,
                          void *out_host, unsigned long out_capacity);
 /* Same, with device pointers, asynchronous on the library stream (no copies, no wait).  The output count is
- * known on the host without a device round-trip.  This is what chains and bench.py use. */
+ * known on the host without a device round-trip.  This is what chains and bench.py use.
+ * Exception: a stage whose output count depends on the data (the sampler, the clocksampler) reads its count word back and waits for its
+ * own kernels; so does a chain holding one (lrhip_chain_execute_device, and lrhip_chain_submit, whose return value is then the exact count). */
 long lrhip_stage_execute_device(lrhip_stage_t *q, const void *in_dev, unsigned long n_in,
                                 void *out_dev, unsigned long out_capacity);
 

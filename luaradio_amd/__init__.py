@@ -14,7 +14,8 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      ComplexPhaseBlock, ComplexToRealBlock, ComplexToImagBlock, ComplexConjugateBlock, RealToComplexBlock,
                      AbsoluteValueBlock, AddConstantBlock, DelayBlock, HilbertTransformBlock, SinglepoleHighpassFilterBlock,
                      FMPreemphasisFilterBlock, FloatToComplexBlock, ComplexToFloatBlock, FrequencyModulatorBlock,
-                     PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock)
+                     PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
+                     ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401
 from . import ipc, meters, procfanout, timeshard  # noqa: F401

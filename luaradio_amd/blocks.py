@@ -592,3 +592,111 @@ class PowerSquelchBlock(Block):
 
     def process(self, x):
         return self._execute(x, self.get_output_type().dtype)
+
+
+# ---- between a filtered baseband and a bit stream (luaradio_amd/csrc/stage_digital.h).  Double parameters travel in the op string as
+# "name:key=value", each value as repr(float), which round-trips every double.
+def digital_op(name, **params):
+    return ":".join([name] + ["%s=%s" % (k, repr(float(v))) for k, v in params.items()])
+
+
+class ZeroCrossingClockRecoveryBlock(Block):
+    """radio/blocks/signal/zerocrossingclockrecovery.lua. ZeroCrossingClockRecoveryBlock(baudrate[, threshold=0.0]): Float32 -> +-1 clock."""
+    name = "ZeroCrossingClockRecoveryBlock"
+
+    def instantiate(self, baudrate, threshold=0.0):
+        assert baudrate is not None, "Missing argument #1 (baudrate)"
+        self.baudrate, self.threshold = baudrate, threshold
+        self.add_type_signature([Input("in", types.Float32)], [Output("out", types.Float32)])
+
+    def op(self):
+        return digital_op("zerocrossingclockrecovery", period=self.get_rate() / self.baudrate, threshold=self.threshold)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip zerocrossingclockrecovery object")
+
+    def process(self, x):
+        return self._execute(x, np.float32)
+
+
+class SamplerBlock(Block):
+    """radio/blocks/signal/sampler.lua. SamplerBlock(): data (ComplexFloat32 or Float32) and a Float32 clock -> data where the clock rises.
+    The output count depends on the clock."""
+    name = "SamplerBlock"
+
+    def instantiate(self):
+        self.add_type_signature([Input("data", types.ComplexFloat32), Input("clock", types.Float32)], [Output("out", types.ComplexFloat32)])
+        self.add_type_signature([Input("data", types.Float32), Input("clock", types.Float32)], [Output("out", types.Float32)])
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_binary_create(b"sampler", int(self.get_input_type() is types.ComplexFloat32)), "Creating lrhip sampler object")
+
+    def process(self, data, clock):
+        import ctypes as C
+        L = _lib.load()
+        data, clock = np.ascontiguousarray(data), np.ascontiguousarray(clock)
+        if data.dtype != self.get_input_type().dtype or clock.dtype != np.float32 or len(data) != len(clock):
+            raise TypeError("Block %s expects %s data and a Float32 clock of equal length" % (self.name, self.get_input_type()))
+        cap = L.lrhip_stage_max_output(self._stage, len(data))
+        out = np.empty(cap, dtype=self.get_output_type().dtype)
+        n = L.lrhip_stage_execute2(self._stage, data.ctypes.data_as(C.c_void_p), clock.ctypes.data_as(C.c_void_p), len(data),
+                                   out.ctypes.data_as(C.c_void_p), cap)
+        _lib.check(n, "%s:process" % self.name)
+        return out[:n]
+
+
+class SlicerBlock(Block):
+    """radio/blocks/signal/slicer.lua. SlicerBlock([threshold=0.0]): Float32 -> Bit, x > threshold."""
+    name = "SlicerBlock"
+
+    def instantiate(self, threshold=0.0):
+        self.threshold = threshold
+        self.add_type_signature([Input("in", types.Float32)], [Output("out", types.Bit)])
+
+    def op(self):
+        return digital_op("slicer", threshold=self.threshold)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip slicer object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
+class DifferentialDecoderBlock(Block):
+    """radio/blocks/signal/differentialdecoder.lua. DifferentialDecoderBlock([invert=false]): Bit -> Bit."""
+    name = "DifferentialDecoderBlock"
+
+    def instantiate(self, invert=False):
+        self.invert = bool(invert)
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.Bit)])
+
+    def op(self):
+        return "differentialdecoder:invert=%d" % int(self.invert)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip differentialdecoder object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
+class ClockSamplerBlock(Block):
+    """SamplerBlock(data = x, clock = ZeroCrossingClockRecoveryBlock(baudrate, threshold)(x)) as one one-input stage ("clocksampler"): the
+    subgraph both the AX.25 and the POCSAG receivers use, without the +-1 clock stream.  Float32 -> Float32, data-dependent count.  A
+    SlicerBlock (and a DifferentialDecoderBlock) right after it in a Chain run in its final pass."""
+    name = "ClockSamplerBlock"
+
+    def instantiate(self, baudrate, threshold=0.0):
+        assert baudrate is not None, "Missing argument #1 (baudrate)"
+        self.baudrate, self.threshold = baudrate, threshold
+        self.add_type_signature([Input("in", types.Float32)], [Output("out", types.Float32)])
+
+    def op(self):
+        return digital_op("clocksampler", period=self.get_rate() / self.baudrate, threshold=self.threshold)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip clocksampler object")
+
+    def process(self, x):
+        return self._execute(x, np.float32)

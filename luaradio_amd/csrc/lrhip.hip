@@ -3,7 +3,9 @@
 #include "../../include/lrhip.h"
 
 #include <cmath>
+#include <map>
 #include <memory>
+#include <string>
 
 #include "common.h"
 #ifndef LRHIP_FIR_D1_NACC
@@ -25,6 +27,7 @@
 #include "kernels_firfft64.h"
 #include "kernels_interp.h"
 #include "kernels_rx.h"
+#include "kernels_digital.h"
 
 using namespace lrhip;
 
@@ -47,6 +50,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_elem3.h"
 #include "stage_rx.h"
 #include "chain.h"
+#include "stage_digital.h"
 
 // =====================================================================================================
 // C ABI
@@ -383,6 +387,18 @@ lrhip_stage_t *lrhip_fmmod_create(double modulation_index)
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex)
 {
     if (!op) { set_error("unary: missing operation name"); return nullptr; }
+    {
+        // the digital blocks carry double parameters in the op string (stage_digital.h)
+        std::string name;
+        std::map<std::string, double> kv;
+        const char *c = strchr(op, ':');
+        const std::string head(op, c ? (size_t)(c - op) : strlen(op));
+        if (c || digital_unary_op(head)) {
+            if (!digital_unary_op(head)) { set_error("unary: unknown operation \"%s\"", op); return nullptr; }
+            if (!parse_op(op, name, kv, digital_keys(head))) return nullptr;
+            return digital_unary_create(name, kv, op);
+        }
+    }
     struct { const char *name; int code, in, out; } T[] = {
         {"complexmagnitude", UN_CMAG, 8, 4}, {"complexphase", UN_CPHASE, 8, 4}, {"complextoreal", UN_CREAL, 8, 4},
         {"complextoimag", UN_CIMAG, 8, 4},   {"complexconjugate", UN_CCONJ, 8, 8}, {"realtocomplex", UN_R2C, 4, 8},
@@ -460,6 +476,16 @@ lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsig
 lrhip_stage_t *lrhip_binary_create(const char *op, int input_complex)
 {
     if (!op) { set_error("binary: missing operation name"); return nullptr; }
+    if (!strcmp(op, "sampler")) {
+        // SamplerBlock: data (ComplexFloat32 / Float32, input_complex) and a Float32 clock; the output count depends on the clock
+        if (ensure_init()) return nullptr;
+        std::unique_ptr<SamplerStage> q(new (std::nothrow) SamplerStage());
+        if (!q) { set_error("out of memory"); return nullptr; }
+        q->in_size = q->out_size = input_complex ? 8 : 4;
+        q->in2_size = 4;
+        if (q->reset()) return nullptr;
+        return q.release();
+    }
     int code = !strcmp(op, "multiply") ? BIN_MULTIPLY : !strcmp(op, "multiplyconjugate") ? BIN_MULTIPLY_CONJ
              : !strcmp(op, "add") ? BIN_ADD : !strcmp(op, "subtract") ? BIN_SUBTRACT : !strcmp(op, "floattocomplex") ? BIN_F2C : -1;
     if (code < 0) { set_error("binary: unknown operation \"%s\"", op); return nullptr; }
@@ -515,14 +541,19 @@ long lrhip_stage_execute2(lrhip_stage_t *q, const void *in1_host, const void *in
     BinaryStage *b = dynamic_cast<BinaryStage *>(q);
     if (!b) return set_error("%s is not a two-input stage", q->kind());
     if (n_in && !in2_host) return set_error("null input buffer");
-    size_t bytes = (size_t)n_in * q->in_size;
+    const int in2_size = q->input2_size();
+    size_t bytes = (size_t)n_in * in2_size;
     if (b->h_in2.reserve(bytes ? bytes : 16) || b->d_in2.reserve(bytes ? bytes : 16)) return -1;
     if (bytes) {
         memcpy(b->h_in2.p, in2_host, bytes);
         LR_HIP(hipMemcpyAsync(b->d_in2.p, b->h_in2.p, bytes, hipMemcpyHostToDevice, ctx().stream));
     }
-    return host_execute(q->h_in, q->h_out, q->d_in, q->d_out, q->in_size, q->out_size, n_in, in1_host, n_in, out_host, out_capacity,
-                        [&](const void *di, unsigned long n, void *dout, unsigned long cap) { return q->run2(di, b->d_in2.p, n, dout, cap); });
+    // (a piece of a long call starts at the same sample of both inputs)
+    return host_execute(q->h_in, q->h_out, q->d_in, q->d_out, q->in_size, q->out_size, q->max_output(n_in), in1_host, n_in, out_host, out_capacity,
+                        [&](const void *di, unsigned long n, void *dout, unsigned long cap) {
+                            const size_t first = (size_t)((const char *)di - (const char *)q->d_in.p) / (size_t)q->in_size;
+                            return q->run2(di, (const char *)b->d_in2.p + first * (size_t)in2_size, n, dout, cap);
+                        });
 }
 
 // ---- chains ---------------------------------------------------------------------------------------------
@@ -905,6 +936,7 @@ lrhip_chain_t *lrhip_chain_create_ex(lrhip_stage_t **stages, unsigned nstages, u
             c->ops.erase(c->ops.begin() + (long)k);
         }
     }
+    if (!(flags & LRHIP_CHAIN_NO_FUSION) && digital_fuse_tail(c->ops)) return nullptr;
     for (size_t k = 0; k + 1 < c->ops.size(); k++) c->edges.emplace_back(new DeviceBuf());
     return c.release();
 }

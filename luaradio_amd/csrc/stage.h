@@ -7,6 +7,8 @@
 // =====================================================================================================
 struct lrhip_stage {
     int in_size = 8, out_size = 8;     // bytes per sample
+    int in2_size = 0;                  // two-input stages whose second input differs from the first (SamplerBlock's clock); 0 = in_size
+    int input2_size() const { return in2_size ? in2_size : in_size; }
     PinnedBuf h_in, h_out;             // pinned staging for the host-pointer execute
     DeviceBuf d_in, d_out;
     virtual ~lrhip_stage() {}

@@ -1,0 +1,325 @@
+// stage_digital.h - ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock and the fused "clocksampler"
+// (kernels_digital.h).  The sampler and the clocksampler are the first stages whose output count depends on the data: run() / run2() return the
+// exact count, read back from the device after the final pass (one small synchronous copy per call).
+// (part of liblrhip.so; included by lrhip.hip after stage_elem2.h, one translation unit)
+#pragma once
+
+// "name:key=value:key=value" -> name and a key -> double map; values through strtod (exact for %.17g / repr() text).  false + lrhip_strerror
+// on a malformed string or a key outside `allowed`.
+static bool parse_op(const char *op, std::string &name, std::map<std::string, double> &kv, std::initializer_list<const char *> allowed)
+{
+    const char *c = strchr(op, ':');
+    name.assign(op, c ? (size_t)(c - op) : strlen(op));
+    while (c) {
+        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
+        if (!eq || (next && eq > next) || eq == k) { set_error("%s: malformed parameter in \"%s\" (expected key=value)", name.c_str(), op); return false; }
+        const std::string key(k, (size_t)(eq - k));
+        bool ok = false;
+        for (const char *a : allowed) ok = ok || key == a;
+        if (!ok) { set_error("%s: unknown parameter \"%s\"", name.c_str(), key.c_str()); return false; }
+        const char *v = eq + 1, *vend = next ? next : v + strlen(v);
+        char *end = nullptr;
+        errno = 0;
+        const double d = strtod(v, &end);
+        if (v == vend || end != vend || errno == ERANGE) { set_error("%s: bad value for \"%s\" in \"%s\"", name.c_str(), key.c_str(), op); return false; }
+        if (kv.count(key)) { set_error("%s: parameter \"%s\" given twice", name.c_str(), key.c_str()); return false; }
+        kv[key] = d;
+        c = next;
+    }
+    return true;
+}
+
+// The clock recovery's closed form (kernels_digital.h) for symbol period P: decided here, and only where it is proven.
+//   P >= 2, 2^e <= P < 2^(e+1) with P + 1 <= 2^(e+1), and P < 2^40.
+//   From each kind of reset the literal loop runs (exactly: an offset >= 1 loses integers without rounding) to its first pulse ks, whose add gives
+//   o1 = fl(o' + P), o' in [0, 1).  If o1 < P + 1 then o1 = A ulp(P) with r0 = A - Pi in [0, U), and by induction every later offset after
+//   an add is Pi + r (r in [0, U)) units of ulp(P): the integer part goes in exact "- 1" steps, the fraction o' in [0, 1) is a multiple of ulp(P),
+//   and o' + P < P + 1 <= 2^(e+1) stays on P's grid - no rounding ever again.  The j-th later pulse is at ks + floor((j Pi + r0) / U), i.e.
+//   sample k >= ks pulses iff ((k - ks + 1) U - r0 - 1) mod Pi < U.
+static void zc_prepare(double P, double T, ZcParams &p)
+{
+    memset(&p, 0, sizeof(p));
+    p.P = P; p.T = T;
+    if (!(P >= 2.0) || !(P < 1099511627776.0)) return;
+    int ex = 0;
+    (void)frexp(P, &ex);
+    const int e = ex - 1;
+    if (P + 1.0 > ldexp(1.0, e + 1)) return;
+    const double u = ldexp(1.0, e - 52);
+    const unsigned long long U = 1ull << (52 - e), Pi = (unsigned long long)(P / u);
+    for (int kind = 0; kind < 2; kind++) {
+        double o = kind ? P * 0.5 : P;
+        long long k = 0;
+        while (o >= 2.0) { const double s = floor(o) - 1.0; o -= s; k += (long long)s; }
+        o = o - 1.0;                                          // o was in [1, 2): this sample pulses
+        const double o1 = o + P;
+        if (!(o >= 0.0) || !(o1 < P + 1.0)) return;
+        const unsigned long long A = (unsigned long long)(o1 / u);
+        if ((double)A * u != o1 || A < Pi || A - Pi >= U) return;
+        const long long r0 = (long long)(A - Pi);
+        __int128 c = (__int128)(1 - k) * (__int128)U - r0 - 1;
+        c %= (__int128)Pi;
+        if (c < 0) c += (__int128)Pi;
+        p.ks[kind] = k;
+        p.c0[kind] = (unsigned long long)c;
+    }
+    p.U = U; p.Pi = Pi;
+    p.closed = 1;
+}
+
+static int dg_state_init(DeviceBuf &state, double P = 0.0)
+{
+    DgState s[2];
+    memset(s, 0, sizeof(s));
+    s[0].h = s[1].h = -1;                                    // hysteresis false / clock LOW
+    s[0].o = s[1].o = P;                                     // zerocrossingclockrecovery.lua:37: the offset starts at one symbol period
+    return upload(state, s, sizeof(s));
+}
+
+// =====================================================================================================
+// ZeroCrossingClockRecoveryBlock, and the fused clocksampler (+ slicer + differential decoder)
+// =====================================================================================================
+struct ZcStage : lrhip_stage {
+    ZcParams p;
+    bool sampler = false;                    // clocksampler: emits x[i] where the recovered clock rises
+    DgTail tail{DG_OUT_FLOAT, 0.0, 0};
+    DeviceBuf state, scratch, staging;
+    PinnedBuf h_count;
+    int cur = 0;
+    const char *kind() const override { return sampler ? "clocksampler" : "zerocrossingclockrecovery"; }
+    long memory() const override { return -1; }
+    int reset() override { cur = 0; return dg_state_init(state, p.P); }
+    unsigned long max_output(unsigned long n) const override { return sampler ? (n + 1) / 2 + 1 : n; }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (!sampler && n > cap) return set_error("%s: output capacity %lu < %lu", kind(), cap, n);
+        if (!n) return 0;
+        const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
+        // scratch: tile summaries, then per-tile h, rpos, kind, literal offset, previous clock, count, last bit
+        const size_t o_h = nt * sizeof(HSum), o_rpos = o_h + nt * 8, o_kind = o_rpos + nt * 8, o_o = o_kind + nt * 8, o_prev = o_o + nt * 8,
+                     o_cnt = o_prev + nt * 8, o_bit = o_cnt + nt * 8, total = o_bit + nt * 8;
+        if (scratch.reserve(total)) return -1;
+        char *sp = (char *)scratch.p;
+        HSum *tiles = (HSum *)sp;
+        int *t_h = (int *)(sp + o_h), *t_kind = (int *)(sp + o_kind), *t_prev = (int *)(sp + o_prev), *t_bit = (int *)(sp + o_bit);
+        long long *t_rpos = (long long *)(sp + o_rpos);
+        double *t_o = (double *)(sp + o_o);
+        unsigned *t_cnt = (unsigned *)(sp + o_cnt);
+        const DgState *si = (const DgState *)state.p + cur;
+        DgState *so = (DgState *)state.p + (cur ^ 1);
+        const float *x = (const float *)in_dev;
+        hipLaunchKernelGGL(zc_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, p.T, tiles);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(zc_carry_kernel, dim3(1), dim3(256), 0, ctx().stream, (const HSum *)tiles, nt, n, p, si, so, t_h, t_rpos, t_kind, t_o, t_prev);
+        LR_LAUNCH_CHECK();
+        if (!sampler) {
+            hipLaunchKernelGGL((zc_emit_kernel<0>), dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, p, tail, out_dev, si, so,
+                               (const int *)t_h, (const long long *)t_rpos, (const int *)t_kind, (const double *)t_o, (const int *)t_prev, t_cnt, t_bit);
+            LR_LAUNCH_CHECK();
+            cur ^= 1;
+            return (long)n;
+        }
+        const unsigned long bound = max_output(n);
+        if (cap < bound) return set_error("%s: output capacity %lu < bound %lu", kind(), cap, bound);
+        // each tile's emitted samples / sliced bits in a slot of DG_TILE / 2 entries (a rising clock edge needs a sample without pulse before it)
+        const size_t esz = tail.out == DG_OUT_FLOAT ? 4 : 1;
+        if (staging.reserve(nt * (DG_TILE / 2) * esz)) return -1;
+        hipLaunchKernelGGL((zc_emit_kernel<1>), dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, p, tail, staging.p, si, so,
+                           (const int *)t_h, (const long long *)t_rpos, (const int *)t_kind, (const double *)t_o, (const int *)t_prev, t_cnt, t_bit);
+        LR_LAUNCH_CHECK();
+        // packing: up to 256 workgroups, each a run of `per` tiles
+        const unsigned long per = (nt + 255) / 256, groups = (nt + per - 1) / per;
+        if (tail.out == DG_OUT_FLOAT)
+            hipLaunchKernelGGL((dg_compact_kernel<DG_OUT_FLOAT>), dim3((unsigned)groups), dim3(256), 0, ctx().stream, (const void *)staging.p, (const unsigned *)t_cnt,
+                               (const int *)t_bit, nt, per, tail, out_dev, cap, si, so);
+        else if (tail.out == DG_OUT_SLICE)
+            hipLaunchKernelGGL((dg_compact_kernel<DG_OUT_SLICE>), dim3((unsigned)groups), dim3(256), 0, ctx().stream, (const void *)staging.p, (const unsigned *)t_cnt,
+                               (const int *)t_bit, nt, per, tail, out_dev, cap, si, so);
+        else
+            hipLaunchKernelGGL((dg_compact_kernel<DG_OUT_DECODE>), dim3((unsigned)groups), dim3(256), 0, ctx().stream, (const void *)staging.p, (const unsigned *)t_cnt,
+                               (const int *)t_bit, nt, per, tail, out_dev, cap, si, so);
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        // the data-dependent count: the one small read-back of this stage
+        if (h_count.reserve(sizeof(unsigned long long))) return -1;
+        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+        LR_HIP(hipStreamSynchronize(ctx().stream));
+        const unsigned long long got = *(const unsigned long long *)h_count.p;
+        if (got > bound) return set_error("%s: %llu outputs exceed the bound %lu", kind(), got, bound);
+        return (long)got;
+    }
+};
+
+// =====================================================================================================
+// SamplerBlock: data (Float32 or ComplexFloat32) and clock (Float32) -> the data type, data-dependent count
+// =====================================================================================================
+struct SamplerStage : BinaryStage {
+    DeviceBuf state, scratch;
+    PinnedBuf h_count;
+    int cur = 0;
+    const char *kind() const override { return "sampler"; }
+    long memory() const override { return -1; }
+    int reset() override { cur = 0; return dg_state_init(state); }
+    unsigned long max_output(unsigned long n) const override { return (n + 1) / 2 + 1; }
+    long run2(const void *data, const void *clk, unsigned long n, void *y, unsigned long cap) override
+    {
+        if (!n) return 0;
+        const unsigned long bound = max_output(n);
+        if (cap < bound) return set_error("sampler: output capacity %lu < bound %lu", cap, bound);
+        const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
+        const size_t o_h = nt * sizeof(SSum), o_off = o_h + nt * 8, total = o_off + nt * 8;
+        if (scratch.reserve(total)) return -1;
+        char *sp = (char *)scratch.p;
+        SSum *tiles = (SSum *)sp;
+        int *t_h = (int *)(sp + o_h);
+        unsigned long long *t_off = (unsigned long long *)(sp + o_off);
+        const DgState *si = (const DgState *)state.p + cur;
+        DgState *so = (DgState *)state.p + (cur ^ 1);
+        hipLaunchKernelGGL(sampler_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, (const float *)clk, n, tiles);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(sampler_carry_kernel, dim3(1), dim3(256), 0, ctx().stream, (const SSum *)tiles, nt, si, so, t_h, t_off);
+        LR_LAUNCH_CHECK();
+        if (in_size == 8)
+            hipLaunchKernelGGL(sampler_final_kernel<2>, dim3((unsigned)nt), dim3(256), 0, ctx().stream, (const float *)data, (const float *)clk, n, (float *)y, cap,
+                               (const int *)t_h, (const unsigned long long *)t_off);
+        else
+            hipLaunchKernelGGL(sampler_final_kernel<1>, dim3((unsigned)nt), dim3(256), 0, ctx().stream, (const float *)data, (const float *)clk, n, (float *)y, cap,
+                               (const int *)t_h, (const unsigned long long *)t_off);
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        if (h_count.reserve(sizeof(unsigned long long))) return -1;
+        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+        LR_HIP(hipStreamSynchronize(ctx().stream));
+        const unsigned long long got = *(const unsigned long long *)h_count.p;
+        if (got > bound) return set_error("sampler: %llu outputs exceed the bound %lu", got, bound);
+        return (long)got;
+    }
+};
+
+// =====================================================================================================
+// SlicerBlock: Float32 -> Bit (1 B), x > threshold in double
+// =====================================================================================================
+struct SlicerStage : lrhip_stage {
+    double t = 0.0;
+    const char *kind() const override { return "slicer"; }
+    int reset() override { return 0; }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (n > cap) return set_error("slicer: output capacity %lu < %lu", cap, n);
+        if (!n) return 0;
+        hipLaunchKernelGGL(slicer_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const float *)in_dev, (uint8_t *)out_dev, n, t);
+        LR_LAUNCH_CHECK();
+        return (long)n;
+    }
+};
+
+// =====================================================================================================
+// DifferentialDecoderBlock: Bit -> Bit, out = prev ^ x (inverted: (prev ^ x + 1) % 2), prev = the previous input byte
+// =====================================================================================================
+struct DiffDecStage : lrhip_stage {
+    int invert = 0;
+    DeviceBuf state;                         // two bytes, ping-pong: the last input byte of the previous call
+    int cur = 0;
+    const char *kind() const override { return "differentialdecoder"; }
+    long memory() const override { return 1; }
+    int reset() override { cur = 0; return zero_fill(state, 2); }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (n > cap) return set_error("differentialdecoder: output capacity %lu < %lu", cap, n);
+        if (!n) return 0;
+        const uint8_t *s = (const uint8_t *)state.p;
+        hipLaunchKernelGGL(diffdec_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const uint8_t *)in_dev, (uint8_t *)out_dev, n, invert,
+                           s + cur, (uint8_t *)state.p + (cur ^ 1));
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        return (long)n;
+    }
+};
+
+// ---- constructors behind lrhip_unary_create / lrhip_binary_create (op strings "name:key=value...")
+static lrhip_stage_t *digital_unary_create(const std::string &name, const std::map<std::string, double> &kv, const char *op)
+{
+    auto need = [&](const char *k, double &v) {
+        auto it = kv.find(k);
+        if (it == kv.end()) { set_error("%s: missing parameter \"%s\" in \"%s\"", name.c_str(), k, op); return false; }
+        v = it->second;
+        return true;
+    };
+    double P = 0.0, T = 0.0, inv = 0.0;
+    if (name == "zerocrossingclockrecovery" || name == "clocksampler") {
+        if (!need("period", P) || !need("threshold", T)) return nullptr;
+        if (!(P > 0.0) || !std::isfinite(P)) { set_error("%s: period must be finite and > 0", name.c_str()); return nullptr; }
+        if (!std::isfinite(T)) { set_error("%s: threshold must be finite", name.c_str()); return nullptr; }
+        if (ensure_init()) return nullptr;
+        std::unique_ptr<ZcStage> q(new (std::nothrow) ZcStage());
+        if (!q) { set_error("out of memory"); return nullptr; }
+        zc_prepare(P, T, q->p);
+        q->sampler = name == "clocksampler";
+        q->in_size = q->out_size = 4;
+        if (q->reset()) return nullptr;
+        return q.release();
+    }
+    if (name == "slicer") {
+        if (!need("threshold", T)) return nullptr;
+        if (ensure_init()) return nullptr;
+        std::unique_ptr<SlicerStage> q(new (std::nothrow) SlicerStage());
+        if (!q) { set_error("out of memory"); return nullptr; }
+        q->t = T;
+        q->in_size = 4; q->out_size = 1;
+        return q.release();
+    }
+    if (name == "differentialdecoder") {
+        if (!need("invert", inv)) return nullptr;
+        if (inv != 0.0 && inv != 1.0) { set_error("differentialdecoder: invert must be 0 or 1"); return nullptr; }
+        if (ensure_init()) return nullptr;
+        std::unique_ptr<DiffDecStage> q(new (std::nothrow) DiffDecStage());
+        if (!q) { set_error("out of memory"); return nullptr; }
+        q->invert = inv != 0.0;
+        q->in_size = q->out_size = 1;
+        if (q->reset()) return nullptr;
+        return q.release();
+    }
+    return nullptr;
+}
+// the keys each op takes (anything else is refused)
+static std::initializer_list<const char *> digital_keys(const std::string &name)
+{
+    static const std::initializer_list<const char *> zc = {"period", "threshold"}, sl = {"threshold"}, dd = {"invert"};
+    return name == "slicer" ? sl : name == "differentialdecoder" ? dd : zc;
+}
+static bool digital_unary_op(const std::string &name)
+{
+    return name == "zerocrossingclockrecovery" || name == "clocksampler" || name == "slicer" || name == "differentialdecoder";
+}
+
+// lrhip_chain_create_ex: clocksampler -> slicer [-> differentialdecoder] becomes ONE clocksampler whose final pass writes the (decoded) bits.  All exact,
+// so in default and EXACT chains alike; not with LRHIP_CHAIN_NO_FUSION.  The fused stage takes over the carried state of the caller's clocksampler and
+// differential decoder (the slicer has none), so a chain built from stages that have already run continues their streams.
+static int digital_fuse_tail(std::vector<lrhip_chain::Op> &ops)
+{
+    for (size_t k = 0; k + 1 < ops.size(); k++) {
+        ZcStage *cs = dynamic_cast<ZcStage *>(ops[k].stage);
+        SlicerStage *sl = dynamic_cast<SlicerStage *>(ops[k + 1].stage);
+        if (!cs || !cs->sampler || cs->tail.out != DG_OUT_FLOAT || !sl) continue;
+        DiffDecStage *dd = k + 2 < ops.size() ? dynamic_cast<DiffDecStage *>(ops[k + 2].stage) : nullptr;
+        std::unique_ptr<ZcStage> f(new (std::nothrow) ZcStage());
+        if (!f) return set_error("out of memory");
+        f->p = cs->p;
+        f->sampler = true;
+        f->tail.out = dd ? DG_OUT_DECODE : DG_OUT_SLICE;
+        f->tail.slice_t = sl->t;
+        f->tail.invert = dd ? dd->invert : 0;
+        f->in_size = 4; f->out_size = 1;
+        if (f->reset()) return -1;
+        // carried state: the clocksampler's, plus the decoder's previous input bit
+        LR_HIP(hipMemcpyAsync((DgState *)f->state.p, (const DgState *)cs->state.p + cs->cur, sizeof(DgState), hipMemcpyDeviceToDevice, ctx().stream));
+        if (dd) LR_HIP(hipMemcpyAsync(&((DgState *)f->state.p)->bit, (const uint8_t *)dd->state.p + dd->cur, 1, hipMemcpyDeviceToDevice, ctx().stream));
+        if (dd) LR_HIP(hipMemsetAsync((char *)&((DgState *)f->state.p)->bit + 1, 0, sizeof(int) - 1, ctx().stream));
+        if (ops[k].owned) delete ops[k].stage;
+        if (ops[k + 1].owned) delete ops[k + 1].stage;
+        if (dd && ops[k + 2].owned) delete ops[k + 2].stage;
+        ops.erase(ops.begin() + (long)k + 1, ops.begin() + (long)k + (dd ? 3 : 2));
+        ops[k] = {f.release(), true};
+    }
+    return 0;
+}

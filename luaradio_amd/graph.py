@@ -276,8 +276,9 @@ class DeviceGraph:
                 tail.out[0][1] = n.runner.process_device(ptrs[0], count, tail.out[0][0].ptr, cap) if count else 0
             elif len(ptrs) == 2:
                 tail = n
-                n.out[0][0].reserve(max(count, 1) * b.get_output_type().size)
-                got = L.lrhip_stage_execute2_device(b.stage_handle(), ptrs[0], ptrs[1], count, n.out[0][0].ptr, count) if count else 0
+                cap = b.max_output(count)                    # a data-dependent count (SamplerBlock) is bounded by max_output, not by the input count
+                n.out[0][0].reserve(max(cap, 1) * b.get_output_type().size)
+                got = L.lrhip_stage_execute2_device(b.stage_handle(), ptrs[0], ptrs[1], count, n.out[0][0].ptr, cap) if count else 0
                 n.out[0][1] = _lib.check(got, "%s:process" % b.name)
             else:
                 tail = n

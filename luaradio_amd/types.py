@@ -1,7 +1,7 @@
 """Sample types - mirrors radio/types/complexfloat32.lua:19-24 and radio/types/float32.lua:17-21.
 
 ComplexFloat32 = struct{float real, imag} (8 B interleaved) == numpy complex64;
-Float32 = struct{float value} (4 B) == numpy float32.  Vectors are contiguous numpy arrays, which is the
+Float32 = struct{float value} (4 B) == numpy float32; Bit = struct{uint8_t value} (1 B) == numpy uint8.  Vectors are contiguous numpy arrays, which is the
 same raw layout the reference writes on its pipes (radio/types/cstruct.lua:87-126).
 """
 import numpy as np
@@ -20,6 +20,8 @@ class _SampleType:
             if a.ndim == 2:       # {{re, im}, ...} as in the reference
                 return (a[:, 0] + 1j * a[:, 1]).astype(np.complex64)
             return np.asarray(arr).astype(np.complex64)
+        if self.dtype == np.uint8:
+            return np.asarray(arr).astype(np.uint8)
         return np.asarray(arr, dtype=np.float64).astype(np.float32)
 
     def __repr__(self):
@@ -28,6 +30,8 @@ class _SampleType:
 
 ComplexFloat32 = _SampleType("ComplexFloat32", np.complex64, 8)
 Float32 = _SampleType("Float32", np.float32, 4)
+# radio/types/bit.lua: struct bit {uint8_t value} (1 B)
+Bit = _SampleType("Bit", np.uint8, 1)
 
 
 def type_of(x):
@@ -37,4 +41,6 @@ def type_of(x):
         return ComplexFloat32
     if x.dtype == np.float32:
         return Float32
-    raise TypeError("Unsupported sample dtype %s (expected complex64 or float32)" % x.dtype)
+    if x.dtype == np.uint8:
+        return Bit
+    raise TypeError("Unsupported sample dtype %s (expected complex64, float32 or uint8)" % x.dtype)
