@@ -7,8 +7,11 @@
 // =====================================================================================================
 struct lrhip_chain {
     struct Op {
-        lrhip_stage *stage;
-        bool owned;
+        lrhip_stage *stage;                   // what runs: a caller's stage, or own.get()
+        std::unique_ptr<lrhip_stage> own;     // a stage this chain built (chain_plan.h)
+        explicit Op(lrhip_stage *borrowed) : stage(borrowed) {}
+        explicit Op(std::unique_ptr<lrhip_stage> built) : stage(built.get()), own(std::move(built)) {}
+        bool built() const { return own != nullptr; }
     };
     std::vector<Op> ops;
     std::vector<std::unique_ptr<DeviceBuf>> edges;   // edges[i] = output of op i (all but the last)
@@ -41,8 +44,6 @@ struct lrhip_chain {
         }
         if (s_in) (void)hipStreamDestroy(s_in);
         if (s_out) (void)hipStreamDestroy(s_out);
-        for (auto &o : ops)
-            if (o.owned) delete o.stage;
     }
 };
 

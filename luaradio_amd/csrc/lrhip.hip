@@ -51,6 +51,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_rx.h"
 #include "chain.h"
 #include "stage_digital.h"
+#include "chain_plan.h"
 
 // =====================================================================================================
 // C ABI
@@ -566,10 +567,6 @@ lrhip_chain_t *lrhip_chain_create_ex(lrhip_stage_t **stages, unsigned nstages, u
         set_error("chain: unknown flag bits 0x%x", flags);
         return nullptr;
     }
-    // the numerical contract is a property of the chain (flags); the environment variables of the same names stay as process-wide
-    // overrides for A/B runs
-    const bool exact_rotator = (flags & LRHIP_CHAIN_EXACT_ROTATOR) != 0;
-    const bool no_fusion = (flags & LRHIP_CHAIN_NO_FUSION) != 0;
     for (unsigned i = 0; i < nstages; i++)
         if (!stages[i]) { set_error("chain: stage %u is null", i); return nullptr; }
     for (unsigned i = 0; i + 1 < nstages; i++)
@@ -581,362 +578,33 @@ lrhip_chain_t *lrhip_chain_create_ex(lrhip_stage_t **stages, unsigned nstages, u
     std::unique_ptr<lrhip_chain> c(new (std::nothrow) lrhip_chain());
     if (!c) { set_error("out of memory"); return nullptr; }
     c->flags = flags;
+    const PlanFlags pf{!(flags & LRHIP_CHAIN_NO_FUSION), (flags & LRHIP_CHAIN_EXACT_ROTATOR) != 0, (flags & LRHIP_CHAIN_NO_POLYPHASE_TAIL) != 0,
+                       !(flags & LRHIP_CHAIN_NO_SINGLE_LAUNCH)};
     // Downsampler(1) is the identity (downsampler.lua:45-56 with factor 1 copies every sample; its index stays 0): it gets no launch of its own
     // (a Tuner / Decimator built with decimation 1) - unless it is the whole chain
     std::vector<lrhip_stage_t *> kept;
-    if (!no_fusion && nstages > 1) {
+    if (pf.fusion && nstages > 1) {
         for (unsigned k = 0; k < nstages; k++) {
             DownsamplerStage *d1 = dynamic_cast<DownsamplerStage *>(stages[k]);
             if (!(d1 && d1->factor == 1)) kept.push_back(stages[k]);
         }
         if (!kept.empty() && kept.size() < nstages) { stages = kept.data(); nstages = (unsigned)kept.size(); }
     }
-    unsigned i = 0;
-    while (i < nstages) {
-        if (no_fusion) {                                    // every block runs its own kernels; edges stay on the device
-            c->ops.push_back({stages[i], false});
-            i++;
-            continue;
-        }
-        // fusion: fir fir ... (ComplexFloat32 stream, every one of them on the overlap-save arithmetic: "fast", or left to the library)  ->  ONE filter with the convolved taps
-        // while they fit the 4096-point kernel (kernels_firfft4k.h: 1 281 taps).  A chain of filters is a filter; overlap-save promises 1e-6 of the exact
-        // result, not the bits of a particular block size, and the merged filter rounds once where the chain rounds per stage.  The reference suite's first
-        // entry (five 256-tap filters back to back, luaradio_benchmark.lua:17-37) = 1 276 taps = one launch instead of five.
-        {
-            static const bool no_cascade = getenv("LRHIP_NO_FIR_CASCADE") != nullptr;      // A/B knob
-            auto mergeable = [](lrhip_stage_t *st) -> FirStage * {
-                FirStage *f = dynamic_cast<FirStage *>(st);
-                return (f && f->S == 2 && f->D == 1 && !f->rot && !f->pre_disc && !f->post_disc && !f->use_fft && f->fft_arith && (f->mode_req == 2 || f->mode_req == 3)) ? f : nullptr;
-            };
-            // (LRHIP_CHAIN_NO_POLYPHASE_TAIL = "keep every block's own arithmetic": the same kind of identity, the same switch)
-            FirStage *f0 = (no_cascade || (flags & LRHIP_CHAIN_NO_POLYPHASE_TAIL)) ? nullptr : mergeable(stages[i]);
-            if (f0 && i + 1 < nstages && mergeable(stages[i + 1])) {
-                // taps in natural order, double, complex (real taps: zero imaginary parts)
-                auto natural = [](const FirStage *f) {
-                    const int ts = f->taps_complex ? 2 : 1;
-                    std::vector<double> h((size_t)2 * f->M, 0.0);
-                    for (int t = 0; t < f->M; t++) {
-                        h[2 * t] = f->taps_rev[(size_t)(f->M - 1 - t) * ts];
-                        if (ts == 2) h[2 * t + 1] = f->taps_rev[(size_t)(f->M - 1 - t) * ts + 1];
-                    }
-                    return h;
-                };
-                std::vector<double> acc = natural(f0);
-                bool cplx = f0->taps_complex;
-                unsigned k = i + 1;
-                while (k < nstages) {
-                    FirStage *fk = mergeable(stages[k]);
-                    if (!fk || acc.size() / 2 + (size_t)fk->M - 1 > 1281) break;
-                    const std::vector<double> h = natural(fk);
-                    std::vector<double> out(acc.size() + h.size() - 2, 0.0);
-                    for (size_t a = 0; a < acc.size() / 2; a++)
-                        for (size_t b = 0; b < h.size() / 2; b++) {
-                            out[2 * (a + b)] += acc[2 * a] * h[2 * b] - acc[2 * a + 1] * h[2 * b + 1];
-                            out[2 * (a + b) + 1] += acc[2 * a] * h[2 * b + 1] + acc[2 * a + 1] * h[2 * b];
-                        }
-                    acc.swap(out);
-                    cplx = cplx || fk->taps_complex;
-                    k++;
-                }
-                if (k > i + 1) {
-                    const unsigned Mm = (unsigned)(acc.size() / 2);
-                    std::vector<float> taps((size_t)Mm * (cplx ? 2 : 1));
-                    for (unsigned t = 0; t < Mm; t++) {
-                        if (cplx) { taps[2 * t] = (float)acc[2 * t]; taps[2 * t + 1] = (float)acc[2 * t + 1]; }
-                        else taps[t] = (float)acc[2 * t];
-                    }
-                    FirStage *merged = fir_build(taps.data(), Mm, cplx ? 1 : 0, 1, 1, 2, false, 0.0);
-                    if (!merged) return nullptr;
-                    c->ops.push_back({merged, true});
-                    i = k;
-                    continue;
-                }
-            }
-        }
-        // fusion: [multiplyconstant(real)] upsampler fir(real taps, plain) [downsampler]  ->  one polyphase resampling launch
-        {
-            static const bool no_resample_fusion = getenv("LRHIP_NO_RESAMPLE_FUSION") != nullptr;      // A/B knob
-            unsigned k = i;
-            MulConstStage *mc = dynamic_cast<MulConstStage *>(stages[k]);
-            if (mc && mc->mode <= 1) k++; else mc = nullptr;
-            UpsamplerStage *up = k < nstages ? dynamic_cast<UpsamplerStage *>(stages[k]) : nullptr;
-            FirStage *rf = (up && k + 1 < nstages) ? dynamic_cast<FirStage *>(stages[k + 1]) : nullptr;
-            // (a filter whose arithmetic was left to the library - use_fft nil, mode 3 - may have picked overlap-save for itself: the polyphase form wins)
-            if (!no_resample_fusion && up && rf && !rf->taps_complex && !rf->use_fft && (!rf->fft_arith || rf->mode_req == 3) && rf->D == 1 && !rf->rot && !rf->pre_disc) {
-                DownsamplerStage *rd = k + 2 < nstages ? dynamic_cast<DownsamplerStage *>(stages[k + 2]) : nullptr;
-                unsigned long D = rd ? rd->factor : 1;
-                int L = (int)up->factor;
-                if (ResampleStage::fits(rf->M, L, D)) {
-                    std::unique_ptr<ResampleStage> q(new (std::nothrow) ResampleStage());
-                    if (!q) { set_error("out of memory"); return nullptr; }
-                    q->S = rf->S; q->M = rf->M; q->L = L; q->D = D;
-                    q->HQ = (rf->M - 1) / L + 1;
-                    q->c = mc ? mc->cr : 1.f;
-                    q->in_size = q->out_size = rf->S * 4;
-                    std::vector<float> taps((size_t)rf->M);
-                    for (int t = 0; t < rf->M; t++) taps[t] = rf->taps_rev[rf->M - 1 - t];
-                    if (upload(q->d_taps, taps.data(), taps.size() * sizeof(float)) || q->reset()) return nullptr;
-                    static const bool no_interp_win = getenv("LRHIP_NO_INTERP_WIN") != nullptr;      // A/B knob: one output per thread (fir_resample_kernel)
-                    if (!no_interp_win && q->S == 2 && q->M == 128 && ((D == 1 && L >= 2 && L <= 5) || ResampleStage::rational_supported(L, D))) {
-                        // tap table of fir_interp_kernel: ttab[s * LP + p] = h[p + (J - 1 - s) L], step 0 = the oldest sample
-                        const int J = (q->M + L - 1) / L, LP = (L + 3) & ~3;
-                        std::vector<float> tt((size_t)J * LP, 0.f);
-                        for (int st = 0; st < J; st++)
-                            for (int p = 0; p < L; p++) {
-                                const int t = p + (J - 1 - st) * L;
-                                if (t < q->M) tt[(size_t)st * LP + p] = taps[t];
-                            }
-                        if (upload(q->d_ttab, tt.data(), tt.size() * sizeof(float))) return nullptr;
-                        q->interp_J = J;
-                    }
-                    c->ops.push_back({q.release(), true});
-                    i = k + 2 + (rd ? 1 : 0);
-                    continue;
-                }
-            }
-        }
-        // fusion: [rotator] fir(real taps, plain) [downsampler]  ->  one decimating Toeplitz-MFMA launch
-        RotatorStage *rot = dynamic_cast<RotatorStage *>(stages[i]);
-        unsigned j = rot ? i + 1 : i;
-        FirStage *fir = j < nstages ? dynamic_cast<FirStage *>(stages[j]) : nullptr;
-        bool fusable_fir = fir && !fir->use_fft && fir->D == 1 && !fir->rot;
-        if (rot && fusable_fir && fir->taps_complex) {      // rotator folding is implemented for real taps only
-            c->ops.push_back({stages[i], false});
-            i++;
-            continue;
-        }
-        DownsamplerStage *ds = (fusable_fir && j + 1 < nstages) ? dynamic_cast<DownsamplerStage *>(stages[j + 1]) : nullptr;
-        // a rotator in front of a filter that does NOT decimate stays a launch of its own: the rotating Toeplitz kernel at D = 1 has no register room left
-        // (112-296 bytes of scratch) and runs 2^26 samples in 0.62 ms, against 0.17 (rotator) + 0.21 (overlap-save) / 0.39 (direct form) for the pair
-        static const bool rot_fir_d1 = getenv("LRHIP_ROT_FIR_FUSE_D1") != nullptr;      // A/B knob: fuse it all the same
-        if (rot && fusable_fir && !ds && !rot_fir_d1) {
-            c->ops.push_back({stages[i], false});
-            i++;
-            continue;
-        }
-        // ... [discriminator]: runs as the epilogue of the persistent kernel (ComplexFloat32 outputs never reach HBM)
-        static const bool no_disc_fusion = getenv("LRHIP_NO_DISC_FUSION") != nullptr;      // A/B knob
-        unsigned after = j + 1 + (ds ? 1 : 0);
-        // a filter that asked for overlap-save arithmetic keeps it when fused with a downsampler (polyphase FFT form, kernels_firdecfft.h)
-        // (only when the caller asked for it explicitly, mode 2: an automatic filter takes the direct form when it decimates - faster here)
-        const bool want_fft = fusable_fir && fir->fft_arith && fir->mode_req == 2 && ds && FirStage::decfft_supported((unsigned)ds->factor, fir->M, fir->S);
-        // overlap-save arithmetic the caller pinned (mode 2) stays; an automatic filter (mode 3) that gets a rotator or a downsampler
-        // fused takes the direct form, and then also the discriminator epilogue
-        const bool fft_pinned = fusable_fir && fir->fft_arith && !(fir->mode_req == 3 && (rot || ds));
-        FmDiscrimStage *dsc_after = (!no_disc_fusion && fusable_fir && fir->S == 2 && !fir->taps_complex && (!fft_pinned || want_fft) && after < nstages)
-                                        ? dynamic_cast<FmDiscrimStage *>(stages[after]) : nullptr;
-        if (fusable_fir && (rot || ds || dsc_after)) {
-            unsigned D = ds ? (unsigned)ds->factor : 1;
-            int ts = fir->taps_complex ? 2 : 1;
-            std::vector<float> taps((size_t)fir->M * ts);
-            for (int t = 0; t < fir->M; t++)
-                for (int cc = 0; cc < ts; cc++) taps[(size_t)t * ts + cc] = fir->taps_rev[(size_t)(fir->M - 1 - t) * ts + cc];
-            bool want_rot = rot && fir->S == 2;
-            FirStage *fused = nullptr;
-            if (want_fft || FirStage::mfma_supported_decim(D) || !rot || (fir->S == 2 && !fir->taps_complex && fir->M + 255 <= DECIM_SPAN_MAX))
-                fused = fir_build(taps.data(), (unsigned)fir->M, fir->taps_complex, fir->S == 2, D, want_fft ? 2 : 0, want_rot, want_rot ? rot->omega : 0.0);
-            if (fused && rot && !want_rot) { delete fused; fused = nullptr; }
-            bool with_disc = fused && dsc_after && fused->can_post_disc();
-            // Round 5 (the receivers OFF the stock shape): the Toeplitz kernel has its discriminator epilogue at decimation 5 / 128 taps only, so
-            // an FM receiver at another input rate (Tuner /4, /8) ran its tuner, the discriminator and their fix-ups as separate launches.  The polyphase-FFT
-            // decimator has the epilogue at every decimation it supports: an AUTOMATIC filter (use_fft nil / "auto": the caller left the arithmetic to the
-            // library) that would otherwise lose the epilogue takes that form - tuner + discriminator stay one launch.  Pinned direct-form filters
-            // (use_fft = false), exact chains and unsupported decimations keep what they had.
-            static const bool no_auto_decfft = getenv("LRHIP_NO_AUTO_DECFFT") != nullptr;      // A/B knob
-            // Measured on 2^26 RF samples, one box (profiles/r05_receiver_shapes.txt): Tuner /4 0.385 -> 0.236 ms (5 -> 2 launches); Tuner /8 0.291 -> 0.367 ms, the
-            // polyphase-FFT form with eight branches is the slower tuner there - so decimation 4 only (2 is unmeasured and stays as it was).
-            if (!no_auto_decfft && fused && dsc_after && !with_disc && !want_fft && fir->mode_req == 3 && ds && D == 4 && !exact_rotator && fir->S == 2 && !fir->taps_complex &&
-                FirStage::decfft_supported(D, fir->M, fir->S)) {
-                FirStage *alt = fir_build(taps.data(), (unsigned)fir->M, fir->taps_complex, true, D, 2, want_rot, want_rot ? rot->omega : 0.0);
-                if (alt && alt->decfft && alt->can_post_disc()) {
-                    delete fused;
-                    fused = alt;
-                    with_disc = true;
-                } else {
-                    delete alt;
-                }
-            }
-            if (fused && !rot && !ds && !with_disc) { delete fused; fused = nullptr; }      // nothing was fused
-            if (fused) {
-                if (exact_rotator) fused->rel_rot = false;     // block-of-8 staging with the stand-alone rotator's phasors: fused == unfused bit for bit
-                if (with_disc) {
-                    fused->post_disc = true;
-                    fused->disc_gain = dsc_after->gain;
-                    fused->out_size = 4;                // ComplexFloat32 in, Float32 out
-                    if (fused->reset()) { delete fused; return nullptr; }
-                }
-                // ... [complex -> real element-wise block] behind an LDS-staged decimator (decimations without a Toeplitz instantiation: the AM / SSB / NBFM
-                // receivers' Tuner(…, 50)): ComplexMagnitude / ComplexPhase / ComplexToReal / ComplexToImag run on the accumulators, one launch less and the
-                // ComplexFloat32 tuner output never reaches HBM; the same Float32 operation on the same Float32 filter outputs = the unfused bits
-                static const bool no_unary_fold = getenv("LRHIP_NO_UNARY_FOLD") != nullptr;      // A/B knob
-                UnaryStage *un = (!no_unary_fold && !with_disc && after < nstages) ? dynamic_cast<UnaryStage *>(stages[after]) : nullptr;
-                const bool with_unary = un && fused->can_post_unary() && (un->op == UN_CMAG || un->op == UN_CPHASE || un->op == UN_CREAL || un->op == UN_CIMAG);
-                if (with_unary) {
-                    fused->post_unary = 1 + un->op;
-                    fused->out_size = 4;
-                }
-                c->ops.push_back({fused, true});
-                i = j + (ds ? 2 : 1) + (with_disc ? 1 : 0) + (with_unary ? 1 : 0);
-                continue;
-            }
-        }
-        // fusion: fir(Float32 stream, real taps) -> first-order iir -> [downsampler]: one launch on the register-window kernel, the
-        // recurrence runs on the filter's accumulators (kernels_firwin.h).  A filter pinned to overlap-save (use_fft 1 / 2) keeps it.
-        {
-            static const bool no_fir_iir_fusion = getenv("LRHIP_NO_FIR_IIR_FUSION") != nullptr;      // A/B knob
-            FirStage *f1 = dynamic_cast<FirStage *>(stages[i]);
-            IirStage *ii = (f1 && i + 1 < nstages) ? dynamic_cast<IirStage *>(stages[i + 1]) : nullptr;
-            if (!no_fir_iir_fusion && ii && f1->S == 1 && !f1->taps_complex && f1->D == 1 && !f1->rot && !f1->pre_disc && !f1->post_disc && !f1->use_fft &&
-                (f1->mode_req == 0 || f1->mode_req == 3) && FirWinRealStage::supported_taps(f1->M) && ii->S == 1 && ii->scan && ii->P == 1 && ii->nb <= 2 &&
-                ii->D == 1 && FirWinRealStage::warm_waves_for((double)ii->seq.a[1] / (double)ii->seq.a[0]) > 0) {
-                DownsamplerStage *ds3 = i + 2 < nstages ? dynamic_cast<DownsamplerStage *>(stages[i + 2]) : nullptr;
-                std::vector<float> taps((size_t)f1->M);
-                for (int t = 0; t < f1->M; t++) taps[t] = f1->taps_rev[f1->M - 1 - t];
-                // With a downsampler behind the recurrence only every D-th output of it is kept, and
-                //     y[n] = u[n] + p y[n-1]   =>   y[n] = sum_{k<D} p^k u[n-k]  +  p^D y[n-D]           (exact identity, p = -a1/a0)
-                // so the kept samples are a DECIMATING filter  g = h * b * (1, p, .., p^(D-1))  followed by the first-order recurrence with
-                // pole p^D at the LOW rate: 1/D of the multiply-adds, and the high-rate audio is never computed.  Same transfer function,
-                // different rounding: <= 1e-6 of the reference's arithmetic (the bar of the IIR blocks), not bit-identical to it.
-                static const bool no_polyphase_tail_env = getenv("LRHIP_NO_POLYPHASE_TAIL") != nullptr;      // A/B knob
-                const bool no_polyphase_tail = no_polyphase_tail_env || (flags & LRHIP_CHAIN_NO_POLYPHASE_TAIL);
-                if (!no_polyphase_tail && ds3 && ds3->factor >= 2 && ds3->factor <= 16) {
-                    const int D = (int)ds3->factor, nbb = ii->nb;
-                    const double a0 = (double)ii->seq.a[0];
-                    const double pp = -(double)(float)((double)ii->seq.a[1] / a0);      // the pole as the IIR kernels round it (IirCoeffs)
-                    std::vector<double> cpoly((size_t)(nbb + D - 1), 0.0);
-                    double pk = 1.0;
-                    for (int k = 0; k < D; k++, pk *= pp)
-                        for (int jb = 0; jb < nbb; jb++) cpoly[(size_t)(k + jb)] += pk * (double)(float)((double)ii->seq.b[jb] / a0);
-                    const int Mg0 = f1->M + nbb + D - 2, Mg = (Mg0 + 3) & ~3;            // zero taps at the far end: a multiple of four for the window kernel
-                    std::vector<float> g((size_t)Mg, 0.f);
-                    for (int t = 0; t < Mg0; t++) {
-                        double acc = 0.0;
-                        for (int c2 = 0; c2 < (int)cpoly.size(); c2++)
-                            if (t - c2 >= 0 && t - c2 < f1->M) acc += (double)taps[(size_t)(t - c2)] * cpoly[(size_t)c2];
-                        g[(size_t)t] = (float)acc;
-                    }
-                    FirStage *fd = fir_build(g.data(), (unsigned)Mg, 0, 0, (unsigned)D, 0, false, 0.0);
-                    const float b2[1] = {1.0f}, a2[2] = {1.0f, (float)(-pk)};          // pk = p^D after the loop
-                    // the low-rate recurrence runs on the filter's accumulators when the window kernel takes this shape ...
-                    if (fd && fd->fuse_iir1(1.0, pk) == 0) {
-                        c->ops.push_back({fd, true});
-                        i += 3;
-                        continue;
-                    }
-                    // ... and as its own launch otherwise - if the pole p^D survives rounding to ONE Float32: that moves the DC gain by
-                    // 2^-24 q / (1 - q), held below 3e-7 here (the fused form above carries the pole as a Float32 pair instead)
-                    const bool pole_ok = std::fabs(pk) * 5.96e-8 <= 3e-7 * (1.0 - std::fabs(pk));
-                    lrhip_stage_t *i2 = (fd && pole_ok) ? lrhip_iir_create(b2, 1, a2, 2, 0) : nullptr;
-                    if (fd && i2) {
-                        c->ops.push_back({fd, true});
-                        c->ops.push_back({i2, true});
-                        i += 3;
-                        continue;
-                    }
-                    delete fd;
-                }
-                // without a (small) decimation the recurrence can run on the accumulators of the D = 1 window kernel: one launch, but slower on
-                // MI355X than overlap-save filter + scan (0.068 against 0.060 ms on the WBFM audio tail) - opt-in, LRHIP_FIR_IIR_WIN=1
-                static const bool fir_iir_win = getenv("LRHIP_FIR_IIR_WIN") != nullptr;
-                FirWinRealStage *fw = fir_iir_win ? firwin_real_build(taps.data(), f1->M, ii->seq.b, ii->nb, ii->seq.a, ii->na, ds3 ? ds3->factor : 1) : nullptr;
-                if (fw) {
-                    c->ops.push_back({fw, true});
-                    i += ds3 ? 3 : 2;
-                    continue;
-                }
-            }
-        }
-        // fusion: discriminator -> overlap-save FIR on the real stream: the discriminator runs in the FFT kernel's load stage
-        {
-            FmDiscrimStage *dsc = dynamic_cast<FmDiscrimStage *>(stages[i]);
-            FirStage *f1 = (dsc && i + 1 < nstages) ? dynamic_cast<FirStage *>(stages[i + 1]) : nullptr;
-            if (!no_disc_fusion && f1 && f1->fft_arith && f1->M <= FirStage::FFT_PART && !f1->use_fft && f1->S == 1 && f1->D == 1 && !f1->rot && !f1->pre_disc) {
-                std::vector<float> taps((size_t)f1->M);
-                for (int t = 0; t < f1->M; t++) taps[t] = f1->taps_rev[f1->M - 1 - t];
-                FirStage *fused = fir_build(taps.data(), (unsigned)f1->M, 0, 0, 1, 2, false, 0.0);
-                if (fused) {
-                    fused->pre_disc = true;
-                    fused->disc_gain = dsc->gain;
-                    fused->in_size = 8;                 // ComplexFloat32 in, Float32 out
-                    if (fused->reset()) { delete fused; return nullptr; }
-                    c->ops.push_back({fused, true});
-                    i += 2;
-                    continue;
-                }
-            }
-        }
-        // fusion: iir (scan path) -> downsampler: the final scan pass stores only the kept samples
-        {
-            IirStage *iir = dynamic_cast<IirStage *>(stages[i]);
-            DownsamplerStage *ds2 = (iir && iir->scan && iir->D == 1 && i + 1 < nstages) ? dynamic_cast<DownsamplerStage *>(stages[i + 1]) : nullptr;
-            if (ds2 && ds2->factor > 1) {
-                IirStage *f = (IirStage *)lrhip_iir_create(iir->seq.b, (unsigned)iir->nb, iir->seq.a, (unsigned)iir->na, iir->S == 2);
-                if (f) {
-                    f->D = ds2->factor;
-                    c->ops.push_back({f, true});
-                    i += 2;
-                    continue;
-                }
-            }
-        }
-        c->ops.push_back({stages[i], false});
-        i++;
+    // fusion (chain_plan.h): at each stage the first rule that applies builds the fused stage; a stage no rule takes runs its own kernels
+    Plan plan{stages, nstages, pf, c->ops};
+    for (unsigned i = 0; i < nstages;) {
+        int used = 0;
+        for (size_t r = 0; pf.fusion && !used && r < sizeof kPlanRules / sizeof kPlanRules[0]; r++) used = kPlanRules[r](plan, i);
+        if (used < 0) return nullptr;
+        if (!used) { c->ops.emplace_back(stages[i]); used = 1; }
+        i += (unsigned)used;
     }
-    // a Toeplitz tuner + discriminator stage directly in front of the pair-mode window filter hands its wave-boundary fix-up to that filter's
-    // staging (kernels_firwin2.h FwcParams::fix_edge): the WBFM receiver is then two launches
-    static const bool no_fixup_fold = getenv("LRHIP_NO_FIXUP_FOLD") != nullptr;      // A/B knob
-    for (size_t k = 0; k + 1 < c->ops.size() && !no_fixup_fold; k++) {
-        FirStage *prod = c->ops[k].owned ? dynamic_cast<FirStage *>(c->ops[k].stage) : nullptr;
-        FirStage *cons = c->ops[k + 1].owned ? dynamic_cast<FirStage *>(c->ops[k + 1].stage) : nullptr;
-        if (prod && cons && prod->post_disc && prod->ksteps != 0 && !prod->decfft && !prod->win_cplx_ok() && cons->iir_fused && cons->win_pair_ok()) {
-            prod->defer_fixup = true;
-            cons->fix_src = prod;
-        }
+    if (pf.fusion) {
+        fold_fixups(c->ops);
+        if (merge_receivers(c->ops, pf)) return nullptr;
+        fold_tuner_records(c->ops);
+        if (digital_fuse_tail(c->ops)) return nullptr;
     }
-    // ... and the two become ONE stage whose run() is a single launch (kernels_rx.h): the discriminator stream stays in LDS.  The stage keeps
-    // both FirStages and their state formats, so the two-launch form remains its fallback (and what LRHIP_CHAIN_NO_SINGLE_LAUNCH selects)
-    for (size_t k = 0; k + 1 < c->ops.size(); k++) {
-        FirStage *prod = c->ops[k].owned ? dynamic_cast<FirStage *>(c->ops[k].stage) : nullptr;
-        FirStage *cons = c->ops[k + 1].owned ? dynamic_cast<FirStage *>(c->ops[k + 1].stage) : nullptr;
-        if (!RxStage::shapes_ok(prod, cons)) continue;
-        std::unique_ptr<RxStage> rx(new (std::nothrow) RxStage());
-        if (!rx) { set_error("out of memory"); return nullptr; }
-        rx->A.reset(prod);
-        rx->B.reset(cons);
-        c->ops[k] = {nullptr, false};                        // ownership has moved: the unique_ptrs delete them
-        c->ops.erase(c->ops.begin() + (long)k + 1);
-        rx->single_launch = !(flags & LRHIP_CHAIN_NO_SINGLE_LAUNCH);
-        // IQFileSource's u8 / s8 / s16le records directly in front of it: the receiver reads them itself (2 or 4 bytes per RF sample instead of a
-        // conversion pass and an 8-byte read); every other format keeps its conversion launch
-        static const bool no_u8_fold = getenv("LRHIP_RX_NO_U8_FOLD") != nullptr;      // A/B knob
-        FormatStage *fs = (k > 0 && !no_u8_fold && !(flags & LRHIP_CHAIN_NO_FUSION)) ? dynamic_cast<FormatStage *>(c->ops[k - 1].stage) : nullptr;
-        const int fcls = fs ? kFormats[fs->fmt].cls : -1;
-        const bool fold = fs && !fs->pack && fs->scalars == 2 && !kFormats[fs->fmt].swap && (fcls == 0 || fcls == 1 || fcls == 3) && !c->ops[k - 1].owned;
-        if (fold) { rx->in_u8 = true; rx->fmt = fs; rx->in_fmt = fcls == 0 ? RX_FMT_U8 : fcls == 1 ? RX_FMT_S8 : RX_FMT_S16LE; }
-        if (rx->prepare()) { c->ops.erase(c->ops.begin() + (long)k); return nullptr; }
-        c->ops[k] = {rx.release(), true};
-        if (fold) { c->ops.erase(c->ops.begin() + (long)k - 1); k--; }
-    }
-    // ... and the same records in front of a plain fused Tuner or Decimator ([rotator +] 128-tap filter + decimation 5, no discriminator: the branch of a
-    // fan-out, TunerBlock / DecimatorBlock on its own; or the LDS-staged decimators of the AM / SSB / NBFM receivers, decimation 9 .. 50): folded into the
-    // kernel's staging (kernels_fir.h FMT)
-    {
-        static const bool no_tuner_fold = getenv("LRHIP_TUNER_NO_RAW_FOLD") != nullptr;      // A/B knob
-        for (size_t k = 0; k + 1 < c->ops.size() && !no_tuner_fold && !(flags & LRHIP_CHAIN_NO_FUSION); k++) {
-            FormatStage *fs = c->ops[k].owned ? nullptr : dynamic_cast<FormatStage *>(c->ops[k].stage);
-            FirStage *tf = c->ops[k + 1].owned ? dynamic_cast<FirStage *>(c->ops[k + 1].stage) : nullptr;
-            if (!fs || !tf || fs->pack || fs->scalars != 2 || kFormats[fs->fmt].swap) continue;
-            const int fcls = kFormats[fs->fmt].cls;
-            if (fcls != 0 && fcls != 1 && fcls != 3) continue;
-            if (tf->post_disc || tf->pre_disc || tf->use_fft || tf->decfft || tf->fft_arith || tf->taps_complex || tf->S != 2 || tf->win_cplx_ok()) continue;
-            if (!((tf->D == 5 && tf->ksteps == 51) || (tf->ksteps == 0 && tf->D > 1 && tf->decim_lds_ok()))) continue;
-            tf->in_fmt = fcls == 0 ? RX_FMT_U8 : fcls == 1 ? RX_FMT_S8 : RX_FMT_S16LE;
-            tf->fmt_stage = fs;
-            tf->in_size = fs->in_size;
-            c->ops.erase(c->ops.begin() + (long)k);
-        }
-    }
-    if (!(flags & LRHIP_CHAIN_NO_FUSION) && digital_fuse_tail(c->ops)) return nullptr;
     for (size_t k = 0; k + 1 < c->ops.size(); k++) c->edges.emplace_back(new DeviceBuf());
     return c.release();
 }

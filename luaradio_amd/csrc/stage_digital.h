@@ -291,35 +291,3 @@ static bool digital_unary_op(const std::string &name)
 {
     return name == "zerocrossingclockrecovery" || name == "clocksampler" || name == "slicer" || name == "differentialdecoder";
 }
-
-// lrhip_chain_create_ex: clocksampler -> slicer [-> differentialdecoder] becomes ONE clocksampler whose final pass writes the (decoded) bits.  All exact,
-// so in default and EXACT chains alike; not with LRHIP_CHAIN_NO_FUSION.  The fused stage takes over the carried state of the caller's clocksampler and
-// differential decoder (the slicer has none), so a chain built from stages that have already run continues their streams.
-static int digital_fuse_tail(std::vector<lrhip_chain::Op> &ops)
-{
-    for (size_t k = 0; k + 1 < ops.size(); k++) {
-        ZcStage *cs = dynamic_cast<ZcStage *>(ops[k].stage);
-        SlicerStage *sl = dynamic_cast<SlicerStage *>(ops[k + 1].stage);
-        if (!cs || !cs->sampler || cs->tail.out != DG_OUT_FLOAT || !sl) continue;
-        DiffDecStage *dd = k + 2 < ops.size() ? dynamic_cast<DiffDecStage *>(ops[k + 2].stage) : nullptr;
-        std::unique_ptr<ZcStage> f(new (std::nothrow) ZcStage());
-        if (!f) return set_error("out of memory");
-        f->p = cs->p;
-        f->sampler = true;
-        f->tail.out = dd ? DG_OUT_DECODE : DG_OUT_SLICE;
-        f->tail.slice_t = sl->t;
-        f->tail.invert = dd ? dd->invert : 0;
-        f->in_size = 4; f->out_size = 1;
-        if (f->reset()) return -1;
-        // carried state: the clocksampler's, plus the decoder's previous input bit
-        LR_HIP(hipMemcpyAsync((DgState *)f->state.p, (const DgState *)cs->state.p + cs->cur, sizeof(DgState), hipMemcpyDeviceToDevice, ctx().stream));
-        if (dd) LR_HIP(hipMemcpyAsync(&((DgState *)f->state.p)->bit, (const uint8_t *)dd->state.p + dd->cur, 1, hipMemcpyDeviceToDevice, ctx().stream));
-        if (dd) LR_HIP(hipMemsetAsync((char *)&((DgState *)f->state.p)->bit + 1, 0, sizeof(int) - 1, ctx().stream));
-        if (ops[k].owned) delete ops[k].stage;
-        if (ops[k + 1].owned) delete ops[k + 1].stage;
-        if (dd && ops[k + 2].owned) delete ops[k + 2].stage;
-        ops.erase(ops.begin() + (long)k + 1, ops.begin() + (long)k + (dd ? 3 : 2));
-        ops[k] = {f.release(), true};
-    }
-    return 0;
-}

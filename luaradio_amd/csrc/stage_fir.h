@@ -10,6 +10,15 @@ struct FirStage : lrhip_stage {
     unsigned D = 1;
     bool use_fft = false;
     std::vector<float> taps_rev;          // host copy, reversed (firfilter.lua:234-238)
+    // the taps in natural order again (what fir_build was given): M taps of 1 (real) or 2 (complex) floats
+    std::vector<float> natural_taps() const
+    {
+        const int ts = taps_complex ? 2 : 1;
+        std::vector<float> h((size_t)M * ts);
+        for (int t = 0; t < M; t++)
+            for (int c = 0; c < ts; c++) h[(size_t)t * ts + c] = taps_rev[(size_t)(M - 1 - t) * ts + c];
+        return h;
+    }
     DeviceBuf d_taps, d_atab, d_ctaps4;
     int ksteps = 0;                       // 0 => MFMA path unavailable for this (M, D)
     int mfma_blocks_per_cu = 0;           // resident workgroups of the persistent kernel (occupancy query, cached)

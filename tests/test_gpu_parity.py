@@ -571,6 +571,10 @@ def test_iir_downsampler_chain_fusion(cplx):
         want = np.concatenate([ref_ds.process(ref_iir.process(x[a:b])) for a, b in cuts])
         assert np.array_equal(got, want), factor
         assert len(got) == (n + factor - 1) // factor
+        # the downsampler runs in the scan's final pass: one launch less than the same blocks unfused, on the same last chunk
+        apart = lr.Chain([make(lr.FMDeemphasisFilterBlock, [75e-6], x, rate=220500.0), make(lr.DownsamplerBlock, [factor], x)], exact=lr._lib.CHAIN_NO_FUSION)
+        apart.process(x[50000:n])
+        assert chain.last_launches < apart.last_launches, factor
 
 
 def test_iir_second_and_fourth_order_scan_large():
