@@ -149,6 +149,12 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      count data-dependent (<= ceil(n/2) + 1).  In a chain a slicer [and a differentialdecoder]
  *                                                      right after it run in its final pass (Bit out), except with LRHIP_CHAIN_NO_FUSION;
  *                                                      the fused stage continues the carried state of the caller's clocksampler and decoder.
+ *   "binaryphasecorrector:num_samples=N[:sample_interval=I]"  (binaryphasecorrector.lua:43-73, I defaults to 32) ComplexFloat32 -> ComplexFloat32:
+ *                                                      x * (cos(-avg), sin(-avg)) rounded to ComplexFloat32, avg = the mean of the phases (clamped to
+ *                                                      [-pi/2, pi/2]) measured at the absolute samples 0, I, 2I, ... over the last N measurements (a window
+ *                                                      that starts as N zeros), in exact fixed-point sums: bit-identical however the stream is cut.  N in
+ *                                                      [1, 2^24], I in [1, 2^31], integers.  A NaN phase makes every later output NaN until reset.
+ *                                                      memory() = N I.  In a chain a complextoreal right after it runs in its rotation pass (Float32 out).
  * The sampler and the clocksampler have memory() -1: chains holding them refuse time partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */

@@ -700,3 +700,24 @@ class ClockSamplerBlock(Block):
 
     def process(self, x):
         return self._execute(x, np.float32)
+
+
+class BinaryPhaseCorrectorBlock(Block):
+    """radio/blocks/signal/binaryphasecorrector.lua. BinaryPhaseCorrectorBlock(num_samples[, sample_interval=32]): ComplexFloat32 ->
+    ComplexFloat32, each sample rotated by minus the mean phase of the last num_samples measurements (one every sample_interval samples,
+    clamped to [-pi/2, pi/2]).  A ComplexToRealBlock right after it in a Chain runs in its rotation pass."""
+    name = "BinaryPhaseCorrectorBlock"
+
+    def instantiate(self, num_samples, sample_interval=32):
+        assert num_samples is not None, "Missing argument #1 (num_samples)"
+        self.num_samples, self.sample_interval = num_samples, sample_interval
+        self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32)])
+
+    def op(self):
+        return digital_op("binaryphasecorrector", num_samples=self.num_samples, sample_interval=self.sample_interval)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 1), "Creating lrhip binaryphasecorrector object")
+
+    def process(self, x):
+        return self._execute(x, np.complex64)

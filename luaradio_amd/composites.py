@@ -452,3 +452,49 @@ def nbfm_receiver(rate=1102500.0, tune_offset=-100e3, deviation=5e3, bandwidth=4
     Tuner(offset, 2*(deviation + bw), 50) -> FrequencyDiscriminator(deviation/bw) -> Lowpass(128, bw)."""
     return _receiver([TunerBlock(tune_offset, 2 * (deviation + bandwidth), 50), B.FrequencyDiscriminatorBlock(deviation / bandwidth),
                       B.LowpassFilterBlock(128, bandwidth)], rate)
+
+
+# ---- digital receivers up to the bit stream.  The framers and decoders behind them (AX25FramerBlock, POCSAGFramerBlock / POCSAGDecoderBlock,
+# VaricodeDecoderBlock) are bit-level state machines and stay in the reference (DESIGN.md §8).
+def ax25_receiver(rate=1e6, tune_offset=-100e3):
+    """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, up to the Bit stream AX25FramerBlock reads:
+    Tuner(offset, 12e3, 80) -> NBFMDemodulator(3e3, 3e3) -> Hilbert(129) -> Translator(-1700) -> Lowpass(128, 750) -> Discriminator(1.25)
+    -> Lowpass(128, 1200) -> ClockSampler(1200) -> Slicer -> DifferentialDecoder(true).  ClockSampler(1200) is the reference's
+    ZeroCrossingClockRecovery(1200) feeding the clock of a Sampler whose data is the same filtered signal (:34-36); the slicer and the
+    decoder run in its final pass."""
+    baudrate = 1200
+    return _receiver([TunerBlock(tune_offset, 12e3, 80), NBFMDemodulator(3e3, 3e3), B.HilbertTransformBlock(129), B.FrequencyTranslatorBlock(-1700),
+                      B.LowpassFilterBlock(128, 750), B.FrequencyDiscriminatorBlock(1.25), B.LowpassFilterBlock(128, baudrate),
+                      B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)], rate)
+
+
+def pocsag_receiver(rate=1e6, tune_offset=-100e3, baudrate=1200):
+    """The compute blocks of examples/rtlsdr_pocsag.lua:14-23,33-41 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`), up to the
+    Bit stream POCSAGFramerBlock reads: Tuner(offset, 12e3, 80), then the space branch ComplexBandpass(129, {3500, 5500}) -> ComplexMagnitude and
+    the mark branch ComplexBandpass(129, {-5500, -3500}) -> ComplexMagnitude, joined by Subtract(mark, space) -> Lowpass(128, baudrate) ->
+    ClockSampler(baudrate) -> Slicer.  g.process(**{"in": x}) returns {"SlicerBlock": bits}."""
+    from .graph import DeviceGraph
+    g = DeviceGraph()
+    src = g.input("in", types.ComplexFloat32, rate)
+    tuner = TunerBlock(tune_offset, 12e3, 80)
+    space_filter, space_magnitude = B.ComplexBandpassFilterBlock(129, [3500, 5500]), B.ComplexMagnitudeBlock()
+    mark_filter, mark_magnitude = B.ComplexBandpassFilterBlock(129, [-5500, -3500]), B.ComplexMagnitudeBlock()
+    subtractor = B.SubtractBlock()
+    g.connect(src, tuner)
+    g.connect(tuner, space_filter, space_magnitude)
+    g.connect(tuner, mark_filter, mark_magnitude)
+    g.connect(mark_magnitude, "out", subtractor, "in1")
+    g.connect(space_magnitude, "out", subtractor, "in2")
+    g.connect(subtractor, B.LowpassFilterBlock(128, baudrate), B.ClockSamplerBlock(baudrate), B.SlicerBlock())
+    return g.initialize()
+
+
+def bpsk31_receiver(rate):
+    """The compute blocks of radio/composites/bpsk31receiver.lua:20-44 as one device chain, up to the Bit stream VaricodeDecoderBlock reads:
+    Lowpass(128, 100) -> RootRaisedCosine(101, 1, 31.25) -> BinaryPhaseCorrector(50) -> ComplexToReal -> ClockSampler(31.25) -> Slicer ->
+    DifferentialDecoder(true).  The reference samples the complex corrected signal at the clock recovered from its real part and then takes
+    the real part (:36-40): the same as sampling the real part, so the chain is linear.  The corrector and ComplexToReal run as one stage, and
+    the slicer and the decoder in the clock sampler's final pass."""
+    baudrate = 31.25
+    return _receiver([B.LowpassFilterBlock(128, 100), B.RootRaisedCosineFilterBlock(101, 1, baudrate), B.BinaryPhaseCorrectorBlock(50),
+                      B.ComplexToRealBlock(), B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)], rate)

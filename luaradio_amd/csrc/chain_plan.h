@@ -264,9 +264,29 @@ static int plan_iir_downsample(Plan &p, unsigned i)
     p.add(std::move(f));
     return 2;
 }
+// binaryphasecorrector -> complextoreal  ->  one phase corrector whose rotation pass stores the real part only (Float32): the same once-rounded
+// component, so exact, in default and EXACT chains alike.  The fused stage takes over the caller's corrector's carried state (window, ring,
+// next measurement, rotation, NaN flag), as digital_fuse_tail does.
+static int plan_phasecorr_real(Plan &p, unsigned i)
+{
+    PhaseCorrStage *pc = p.at<PhaseCorrStage>(i);
+    UnaryStage *un = pc && !pc->real_out ? p.at<UnaryStage>(i + 1) : nullptr;
+    if (!un || un->op != UN_CREAL) return 0;
+    std::unique_ptr<PhaseCorrStage> f(new (std::nothrow) PhaseCorrStage());
+    if (!f) return set_error("out of memory");
+    f->p = pc->p;
+    f->real_out = true;
+    f->in_size = 8; f->out_size = 4;
+    if (f->reset()) return -1;
+    LR_HIP(hipMemcpyAsync(f->state.p, (const PcState *)pc->state.p + pc->cur, sizeof(PcState), hipMemcpyDeviceToDevice, ctx().stream));
+    LR_HIP(hipMemcpyAsync(f->ring.p, pc->ring.p, (size_t)pc->p.N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx().stream));
+    f->off = pc->off;
+    p.add(std::move(f));
+    return 2;
+}
 // the rules in the order they are tried at each stage (the first that applies wins: the cascade must see filters before the tuner rule does)
 static int (*const kPlanRules[])(Plan &, unsigned) = {plan_fir_cascade, plan_resample, plan_tuner, plan_polyphase_tail, plan_fir_iir_win, plan_disc_fir,
-                                                      plan_iir_downsample};
+                                                      plan_iir_downsample, plan_phasecorr_real};
 // ---- passes over the planned ops ----------------------------------------------------------------------------------------------------------------
 // the RX_FMT_* of IQFileSource records a kernel can read in place (u8 / s8 / s16le I/Q), from a caller's format stage; 0: none
 static int raw_record_fmt(const lrhip_chain::Op &o)

@@ -28,6 +28,7 @@
 #include "kernels_interp.h"
 #include "kernels_rx.h"
 #include "kernels_digital.h"
+#include "kernels_phasecorr.h"
 
 using namespace lrhip;
 
@@ -50,6 +51,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_elem3.h"
 #include "stage_rx.h"
 #include "chain.h"
+#include "stage_phasecorr.h"
 #include "stage_digital.h"
 #include "chain_plan.h"
 

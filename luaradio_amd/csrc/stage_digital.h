@@ -246,6 +246,7 @@ static lrhip_stage_t *digital_unary_create(const std::string &name, const std::m
         return true;
     };
     double P = 0.0, T = 0.0, inv = 0.0;
+    if (name == "binaryphasecorrector") return phasecorr_create(kv, op);
     if (name == "zerocrossingclockrecovery" || name == "clocksampler") {
         if (!need("period", P) || !need("threshold", T)) return nullptr;
         if (!(P > 0.0) || !std::isfinite(P)) { set_error("%s: period must be finite and > 0", name.c_str()); return nullptr; }
@@ -284,10 +285,12 @@ static lrhip_stage_t *digital_unary_create(const std::string &name, const std::m
 // the keys each op takes (anything else is refused)
 static std::initializer_list<const char *> digital_keys(const std::string &name)
 {
-    static const std::initializer_list<const char *> zc = {"period", "threshold"}, sl = {"threshold"}, dd = {"invert"};
-    return name == "slicer" ? sl : name == "differentialdecoder" ? dd : zc;
+    static const std::initializer_list<const char *> zc = {"period", "threshold"}, sl = {"threshold"}, dd = {"invert"},
+                                                     pc = {"num_samples", "sample_interval"};
+    return name == "slicer" ? sl : name == "differentialdecoder" ? dd : name == "binaryphasecorrector" ? pc : zc;
 }
 static bool digital_unary_op(const std::string &name)
 {
-    return name == "zerocrossingclockrecovery" || name == "clocksampler" || name == "slicer" || name == "differentialdecoder";
+    return name == "zerocrossingclockrecovery" || name == "clocksampler" || name == "slicer" || name == "differentialdecoder" ||
+           name == "binaryphasecorrector";
 }

@@ -1,0 +1,32 @@
+#!/usr/bin/env python3
+"""Golden vectors of BinaryPhaseCorrectorBlock, converted from the reference's committed ``*.gen.lua`` with make_golden.py's parser.
+
+Run in the build container (needs the reference tree, LUARADIO_REFERENCE):
+
+    python tests/golden/make_golden_phasecorr.py
+
+Same schema as make_golden.py.
+"""
+import gzip
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from make_golden import HERE, REF, parse_block_spec  # noqa: E402
+
+SPEC = "blocks/signal/binaryphasecorrector_spec"
+
+
+def main():
+    with open(os.path.join(REF, "tests", SPEC + ".gen.lua")) as f:
+        doc = parse_block_spec(f.read())
+    doc["source"] = "tests/" + SPEC + ".gen.lua"
+    out = os.path.join(HERE, os.path.basename(SPEC) + ".json.gz")
+    with gzip.GzipFile(out, "wb", mtime=0) as f:       # mtime=0: byte-stable across regenerations
+        f.write(json.dumps(doc, separators=(",", ":")).encode())
+    print("%-55s -> %s (%d entries)" % (doc["source"], os.path.basename(out), len(doc["vectors"])))
+
+
+if __name__ == "__main__":
+    sys.exit(main())

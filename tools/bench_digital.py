@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Device throughput of the digital tail (luaradio_amd/csrc/kernels_digital.h) on one MI355X: the fused clocksampler -> slicer -> differential
-decoder chain and the clock recovery alone, on resident Float32 samples.  HIP-event timing on the launch stream after warm-up, as
+decoder chain and the clock recovery alone, on resident Float32 samples; the binary phase corrector (kernels_phasecorr.h) alone on resident
+ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the three digital receivers up to their bit streams.  HIP-event timing on the launch stream after warm-up, as
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
 (4 B/sample read; + 4 B/sample written for the clock recovery)."""
 import argparse
@@ -56,6 +57,45 @@ def main():
         L.lrhip_chain_destroy(ch)
         for s in stages:
             L.lrhip_stage_destroy(s)
+
+    # ---- the binary phase corrector: 8 B/sample read + 8 B/sample written, plus one strided 8-B read per measurement
+    xc = torch.from_numpy((rng.standard_normal(2 * n).astype(np.float32))).cuda().view(torch.complex64)
+    yc = torch.empty_like(xc)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps
+
+    ms = timed(lambda: yc.copy_(xc))
+    print(json.dumps({"row": "copy 16 B/sample (same buffers)", "samples": n, "ms": round(ms, 4), "roof_fraction": round(16.0 * n / (ms * 1e-3) / 8e12, 3)}))
+    for N, I in [(3000, 32), (50, 32)]:
+        op = digital_op("binaryphasecorrector", num_samples=N, sample_interval=I)
+        st = _lib.check_ptr(L.lrhip_unary_create(op.encode(), 0.0, 0.0, 0, 1), op)
+        ms = timed(lambda: _lib.check(L.lrhip_stage_execute_device(st, xc.data_ptr(), n, yc.data_ptr(), n), op))
+        print(json.dumps({"row": "binaryphasecorrector N=%d I=%d" % (N, I), "samples": n, "ms": round(ms, 4),
+                          "roof_fraction": round((16.0 + 8.0 / I) * n / (ms * 1e-3) / 8e12, 3)}))
+        L.lrhip_stage_destroy(st)
+
+    # ---- the receivers, input resident on the device (the POCSAG graph takes host vectors: its time includes the copies in and out)
+    m = min(n, 1 << 24)
+    out = torch.empty(m + 64, dtype=torch.uint8, device="cuda")
+    for name, rx, rate in [("ax25_receiver", lr.ax25_receiver(), 1e6), ("bpsk31_receiver", lr.bpsk31_receiver(1000.0), 1000.0)]:
+        cap = rx.max_output(m)
+        ms = timed(lambda: rx.process_device(xc.data_ptr(), m, out.data_ptr(), cap))
+        print(json.dumps({"row": name, "samples": m, "rate": rate, "ms": round(ms, 4), "launches": rx.chain.last_launches,
+                          "MS/s": round(m / ms / 1e3, 1)}))
+    g = lr.pocsag_receiver()
+    xh = xc[:m].cpu().numpy()
+    ms = timed(lambda: g.process(**{"in": xh}))
+    print(json.dumps({"row": "pocsag_receiver (host vectors)", "samples": m, "rate": 1e6, "ms": round(ms, 4), "MS/s": round(m / ms / 1e3, 1)}))
 
 
 if __name__ == "__main__":

@@ -53,16 +53,16 @@ def main():
         L.lrhip_timer_destroy(t)
         return ms
 
-    def mk(cls, a, cplx, rate=1.0):
+    def mk(cls, a, cplx, rate=1.0, in_type=None):
         b = cls(*a)
         b.rate = rate
-        b.differentiate([types.ComplexFloat32 if cplx else types.Float32])
+        b.differentiate([in_type or (types.ComplexFloat32 if cplx else types.Float32)])
         b.initialize()
         return b
 
     rows = []
 
-    def run(name, published, blk, cplx, third=False):
+    def run(name, published, blk, cplx, third=False, x=None):
         if args.trials > 0:
             from luaradio_amd import meters
             src = lr.ZeroSource(types.ComplexFloat32 if cplx else types.Float32, 1.0, n)
@@ -82,7 +82,7 @@ def main():
                          "trials": args.trials, "reference_i5_MS/s": published,
                          "ratio": round(r["samples_per_second"] / 1e6 / published, 1) if published else None})
             return
-        x = xc if cplx else xr
+        x = x if x is not None else (xc if cplx else xr)
         nin = n // 3 if third else n           # (an upsampler's output has to fit the output vector)
         cap = blk.max_output(nin)
         ms = timeit(lambda: blk.process_device(x.data_ptr(), nin, out.data_ptr(), cap))
@@ -119,6 +119,13 @@ def main():
     run("Hilbert Transform (65 taps)", 67.66, mk(lr.HilbertTransformBlock, [65], False), False)
     run("Hilbert Transform (129 taps)", 47.47, mk(lr.HilbertTransformBlock, [129], False), False)
     run("Frequency Discriminator", 111.61, mk(lr.FrequencyDiscriminatorBlock, [1.25], True), True)
+    # the digital entries (luaradio_benchmark.lua:399-420, 569-590): uniform random input, Bit input as random 0 / 1 bytes
+    run("Zero Crossing Clock Recovery", 71.96, mk(lr.ZeroCrossingClockRecoveryBlock, [1200], False, 1e6), False)
+    run("Binary Phase Corrector", 54.76, mk(lr.BinaryPhaseCorrectorBlock, [3000], True), True)
+    run("Bit Slicer", 92.64, mk(lr.SlicerBlock, [], False), False)
+    if args.trials == 0:
+        bits = torch.randint(0, 2, (n,), dtype=torch.uint8, device="cuda", generator=g)
+        run("Differential Decoder", 157.30, mk(lr.DifferentialDecoderBlock, [], False, in_type=types.Bit), False, x=bits)
 
     # the element-wise entries (luaradio_benchmark.lua:422-625): the reference feeds both inputs of a two-input block from one source
     def mk2(cls, cplx):
