@@ -179,6 +179,11 @@ long lrhip_welch_read(lrhip_stage_t *q, float *avg_host, int reset);
  * nchannels in {32, 64}; ntaps a multiple of 32. */
 lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels);
 
+/* The same filterbank (same frames, same emission rule and carried index) in its polyphase + FFT form: P = ceil(ntaps / nchannels)
+ * real-by-complex multiply-adds per sample and one inverse DFT of nchannels points per frame, instead of the GEMM's 8 * ntaps flop
+ * per sample.  nchannels a power of two in [8, 4096]; nchannels <= ntaps <= min(64 * nchannels, 65536), any value in between. */
+lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels);
+
 void lrhip_stage_destroy(lrhip_stage_t *q);
 /* Back to the just-created state (zero history, phase 0, index 0). */
 int lrhip_stage_reset(lrhip_stage_t *q);

@@ -11,9 +11,15 @@
 -- position c of its frame, one frame per K input samples - so the port carries rate samples per second in total and each channel runs at rate / K.
 -- K in {32, 64}; #taps a multiple of 32.  Without the library the constructor raises (there is no host implementation to fall back to).
 --
+-- options.method = "fft" evaluates the same filterbank in its polyphase + FFT form (lrhip_pfb_channelizer_create): K a power of two in [8, 4096],
+-- K <= #taps <= min(64 K, 65536), ~50x less arithmetic.  "gemm" asks for the GEMM.  Without a method the GEMM runs where it accepts the shape
+-- and the FFT form everywhere else.
+--
 -- @block PolyphaseChannelizerBlock
 -- @tparam int num_channels Number of channels K
 -- @tparam array|vector taps Real-valued prototype lowpass taps (e.g. radio.utilities.filter_utils.firwin_lowpass(16 * K, 1 / K))
+-- @tparam[opt={}] table options Additional options, specifying:
+--                         * `method` (string, "gemm" or "fft")
 
 local ffi = require('ffi')
 
@@ -23,7 +29,7 @@ local lrhip = require('radio.core.lrhip')
 
 local PolyphaseChannelizerBlock = block.factory("PolyphaseChannelizerBlock")
 
-function PolyphaseChannelizerBlock:instantiate(num_channels, taps)
+function PolyphaseChannelizerBlock:instantiate(num_channels, taps, options)
     assert(lrhip.available, "PolyphaseChannelizerBlock needs liblrhip.so")
     self.num_channels = assert(num_channels, "Missing argument #1 (num_channels)")
     assert(taps, "Missing argument #2 (taps)")
@@ -33,6 +39,8 @@ function PolyphaseChannelizerBlock:instantiate(num_channels, taps)
         assert(taps.data_type == types.Float32, "Unsupported taps type")
         self.taps = taps
     end
+    self.method = (options or {}).method
+    assert(self.method == nil or self.method == "gemm" or self.method == "fft", "Unsupported method (\"gemm\" or \"fft\")")
     self:add_type_signature({block.Input("in", types.ComplexFloat32)}, {block.Output("out", types.ComplexFloat32)})
 end
 
@@ -42,8 +50,21 @@ end
 
 local M = {PolyphaseChannelizerBlock = PolyphaseChannelizerBlock}
 
+-- Does this liblrhip.so have the FFT form?  These files are copied into a LuaRadio checkout and may meet an older library there; LuaJIT raises on the
+-- first index of a symbol the library lacks.  So the entry point is called once, when this file loads, with a shape it refuses before it looks at the
+-- device (no channels: a null result, nothing created, no device context).  Without it the block is the GEMM alone, as it was.
+M.has_fft = lrhip.available and pcall(function ()
+    return lrhip.lib.lrhip_pfb_channelizer_create(nil, 0, 0)
+end)
+
 function M.patch(Block)
     lrhip.device_block(Block, function (self)
+        local k, m = self.num_channels, self.taps.length
+        local gemm_accepts = (k == 32 or k == 64) and m >= 32 and m <= 8192 and m % 32 == 0
+        assert(self.method ~= "fft" or M.has_fft, "this liblrhip.so has no lrhip_pfb_channelizer_create (method = \"fft\")")
+        if M.has_fft and (self.method == "fft" or (self.method == nil and not gemm_accepts)) then
+            return lrhip.lib.lrhip_pfb_channelizer_create(ffi.cast("const float *", self.taps.data), self.taps.length, self.num_channels)
+        end
         return lrhip.lib.lrhip_channelizer_create(ffi.cast("const float *", self.taps.data), self.taps.length, self.num_channels)
     end)
     function Block:process(x)

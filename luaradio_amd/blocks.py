@@ -328,25 +328,36 @@ class UpsamplerBlock(Block):
 
 class PolyphaseChannelizerBlock(Block):
     """Critically sampled K-channel analysis filterbank (BASELINE.json configs[4]).  Not a block of the reference: it is
-    K parallel chains FrequencyTranslatorBlock(-c*rate/K) -> FIRFilterBlock(taps) -> DownsamplerBlock(K), evaluated as
-    one dense GEMM on the f32 matrix cores.  PolyphaseChannelizerBlock(num_channels[, taps]); default prototype =
-    firwin_lowpass(16*K, 1/K).  Output: frames of K ComplexFloat32 (channel c at position c), one per K inputs."""
+    K parallel chains FrequencyTranslatorBlock(-c*rate/K) -> FIRFilterBlock(taps) -> DownsamplerBlock(K).
+    PolyphaseChannelizerBlock(num_channels[, taps[, options]]); default prototype = firwin_lowpass(16*K, 1/K).
+    Output: frames of K ComplexFloat32 (channel c at position c), one per K inputs.
+    options = {"method": "gemm" | "fft"}: "gemm" is one dense GEMM on the f32 matrix cores (K in {32, 64}, len(taps) a multiple
+    of 32 up to 8192), "fft" the polyphase + FFT form (K a power of two in [8, 4096], K <= len(taps) <= min(64 K, 65536)).
+    Without a method: the GEMM where it accepts the shape, the FFT form otherwise."""
     name = "PolyphaseChannelizerBlock"
 
-    def instantiate(self, num_channels, taps=None):
+    def instantiate(self, num_channels, taps=None, options=None):
         assert num_channels, "Missing argument #1 (num_channels)"
         self.num_channels = int(num_channels)
         if taps is None:
             taps = filter_utils.firwin_lowpass(16 * self.num_channels, 1.0 / self.num_channels)
         self.taps = types.Float32.vector_from_array(taps)
+        self.method = (options or {}).get("method")
+        assert self.method in (None, "gemm", "fft"), "Unsupported method \"%s\" (\"gemm\" or \"fft\")" % self.method
         self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32)])
 
     def get_rate(self):
         return Block.get_rate(self)      # K values per K input samples; each channel runs at rate/K
 
+    def gemm_accepts(self):
+        """the domain of lrhip_channelizer_create"""
+        return self.num_channels in (32, 64) and 32 <= len(self.taps) <= 8192 and len(self.taps) % 32 == 0
+
     def initialize(self):
-        self._set_stage(_lib.load().lrhip_channelizer_create(_fptr(self.taps), len(self.taps), self.num_channels),
-                        "Creating lrhip channelizer object")
+        L = _lib.load()
+        fft = self.method == "fft" or (self.method is None and not self.gemm_accepts())
+        create = L.lrhip_pfb_channelizer_create if fft else L.lrhip_channelizer_create
+        self._set_stage(create(_fptr(self.taps), len(self.taps), self.num_channels), "Creating lrhip channelizer object")
 
     def process(self, x):
         """returns an array of shape (frames, K)"""

@@ -18,6 +18,7 @@
 #include "kernels_firdecfft.h"
 #include "kernels_firdecim.h"
 #include "kernels_channelizer.h"
+#include "kernels_pfb.h"
 #include "kernels_iir.h"
 #include "kernels_agc.h"
 #include "kernels_firwin.h"
@@ -48,6 +49,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_spectrum.h"
 #include "stage_elem2.h"
 #include "stage_resample.h"
+#include "stage_pfb.h"
 #include "stage_elem3.h"
 #include "stage_rx.h"
 #include "chain.h"
@@ -472,6 +474,27 @@ lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsig
             W[(size_t)(2 * i + 1) * K2 + 2 * c + 1] = gr;
         }
     if (upload(q->W, W.data(), W.size() * sizeof(float))) return nullptr;
+    if (q->reset()) return nullptr;
+    return q.release();
+}
+
+lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels)
+{
+    if (const char *why = PfbChannelizerStage::refusal(taps ? ntaps : 0, nchannels)) { set_error("%s", why); return nullptr; }
+    if (ensure_init()) return nullptr;
+    std::unique_ptr<PfbChannelizerStage> q(new (std::nothrow) PfbChannelizerStage());
+    if (!q) { set_error("out of memory"); return nullptr; }
+    const int M = (int)ntaps, K = (int)nchannels;
+    q->M = M; q->K = K; q->P = (M + K - 1) / K;
+    while ((1 << q->log2k) < K) q->log2k++;
+    q->in_size = q->out_size = 8;
+    std::vector<float> tw((size_t)K);      // W_K^m = exp(-2 pi i m / K), m < K / 2 (kernels_fft.h), computed in double
+    for (int m = 0; m < K / 2; m++) {
+        double ang = -2.0 * 3.14159265358979323846 * m / K;
+        tw[2 * m] = (float)std::cos(ang);
+        tw[2 * m + 1] = (float)std::sin(ang);
+    }
+    if (upload(q->taps, taps, (size_t)M * sizeof(float)) || upload(q->tw, tw.data(), tw.size() * sizeof(float))) return nullptr;
     if (q->reset()) return nullptr;
     return q.release();
 }

@@ -212,6 +212,36 @@ def main():
     rows.append({"block": "PolyphaseChannelizer K=64, 1024 taps (dense MFMA GEMM)", "MS/s": round(nch / ms / 1e3, 1),
                  "alg_GB/s": round(16 * nch / ms / 1e6, 1), "frac_8TB/s": round(16 * nch / ms / 1e6 / 8000, 4), "ms": round(ms, 4),
                  "TFLOP/s": round(tf, 2), "mfma_util_vs_157.3TF": round(tf / 157.3, 4)})
+    # the same filterbank in its polyphase + FFT form (method = "fft"), head to head: same process, same buffers, the GEMM, the FFT form and the streaming
+    # yardstick (MultiplyConstant cf32, 16 B per sample like this block) alternating; every run listed, so the spread is on the row
+    xs = torch.rand(2 * nch, device="cuda", generator=g) * 2 - 1        # uniform(-1, 1) like xc, but separate from the buffers of the rows above
+    pfb = mk(lr.PolyphaseChannelizerBlock, [64, None, {"method": "fft"}], True)
+    mc = mk(lr.MultiplyConstantBlock, [1.0], True)
+    runs = {"gemm": [], "fft": [], "stream": []}
+    for _ in range(4):
+        runs["gemm"].append(timeit(lambda: ch.process_device(xs.data_ptr(), nch, big.data_ptr(), cap), reps=3))
+        runs["fft"].append(timeit(lambda: pfb.process_device(xs.data_ptr(), nch, big.data_ptr(), cap), reps=10))
+        runs["stream"].append(timeit(lambda: mc.process_device(xs.data_ptr(), nch, big.data_ptr(), cap), reps=10))
+    stream_ms = sorted(runs["stream"])[len(runs["stream"]) // 2]
+
+    def median(v):
+        return sorted(v)[len(v) // 2]
+
+    def pfb_row(name, ms_runs, extra):
+        ms_ = median(ms_runs)
+        row = {"block": name, "MS/s": round(nch / ms_ / 1e3, 1), "alg_GB/s": round(16 * nch / ms_ / 1e6, 1), "frac_8TB/s": round(16 * nch / ms_ / 1e6 / 8000, 4),
+               "ms": round(ms_, 4), "ms_runs": [round(v, 4) for v in ms_runs], "frac_of_streaming_yardstick": round(stream_ms / ms_, 3)}
+        row.update(extra)
+        rows.append(row)
+
+    pfb_row("MultiplyConstant(1.0) cf32 on the channelizer's buffers (streaming yardstick, alternating)", runs["stream"], {})
+    pfb_row("PolyphaseChannelizer K=64, 1024 taps (dense MFMA GEMM, alternating)", runs["gemm"], {})
+    pfb_row("PolyphaseChannelizer K=64, 1024 taps (polyphase + FFT)", runs["fft"],
+            {"speedup_vs_gemm": round(median(runs["gemm"]) / median(runs["fft"]), 2), "gemm_spread_ms": round(max(runs["gemm"]) - min(runs["gemm"]), 4)})
+    for k_, m_ in ((256, 4096), (1024, 16384), (4096, 65536)):
+        blk = mk(lr.PolyphaseChannelizerBlock, [k_, lr.filter_utils.firwin_lowpass(m_, 1.0 / k_), {"method": "fft"}], True)
+        pfb_row("PolyphaseChannelizer K=%d, %d taps (polyphase + FFT)" % (k_, m_),
+                [timeit(lambda: blk.process_device(xs.data_ptr(), nch, big.data_ptr(), cap), reps=10) for _ in range(4)], {})
     for r in rows:
         print(json.dumps(r))
 
