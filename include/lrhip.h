@@ -184,6 +184,15 @@ lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsig
  * per sample.  nchannels a power of two in [8, 4096]; nchannels <= ntaps <= min(64 * nchannels, 65536), any value in between. */
 lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels);
 
+/* The polyphase + FFT filterbank oversampled by R = oversample in {1, 2, 4}: K parallel chains FrequencyTranslatorBlock(-c*fs/K) ->
+ * FIRFilterBlock(taps) -> DownsamplerBlock(D), D = nchannels / R, so that a prototype whose skirt reaches past fs / (2 K) no longer aliases
+ * into its channel.  One frame of K values per D input samples (frame m as soon as sample m D has arrived), each channel at R fs / K:
+ *     y_c[m] = exp(-j 2 pi c m D / K) * sum_{i<ntaps} taps[i] * x[m D - i] * exp(+j 2 pi c i / K)
+ * Frame m R is frame m of the critically sampled bank.  Same domain as lrhip_pfb_channelizer_create (nchannels = 8 with R = 4 included);
+ * oversample = 1 is that stage.  The carried state is the index, the last ntaps - 1 samples and the frame count modulo R.
+ * max_output(n) = (n / D + 1) * K. */
+lrhip_stage_t *lrhip_pfb_oversampled_create(const float *taps, unsigned ntaps, unsigned nchannels, unsigned oversample);
+
 void lrhip_stage_destroy(lrhip_stage_t *q);
 /* Back to the just-created state (zero history, phase 0, index 0). */
 int lrhip_stage_reset(lrhip_stage_t *q);

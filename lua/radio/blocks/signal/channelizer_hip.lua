@@ -15,11 +15,17 @@
 -- K <= #taps <= min(64 K, 65536), ~50x less arithmetic.  "gemm" asks for the GEMM.  Without a method the GEMM runs where it accepts the shape
 -- and the FFT form everywhere else.
 --
+-- options.oversample = 2 or 4 makes the hop D = K / oversample instead of K: one frame per D input samples, each channel at oversample * rate / K and
+-- the port at oversample * rate, so that the prototype's skirt past rate / (2 K) no longer aliases into the channel and a carrier between two
+-- channel centres comes out clean of either neighbour.  Frame m * oversample is frame m of the critically sampled bank.  The FFT form only
+-- (lrhip_pfb_oversampled_create); "gemm" with oversample > 1 raises.
+--
 -- @block PolyphaseChannelizerBlock
 -- @tparam int num_channels Number of channels K
 -- @tparam array|vector taps Real-valued prototype lowpass taps (e.g. radio.utilities.filter_utils.firwin_lowpass(16 * K, 1 / K))
 -- @tparam[opt={}] table options Additional options, specifying:
 --                         * `method` (string, "gemm" or "fft")
+--                         * `oversample` (int, 1, 2 or 4; default 1)
 
 local ffi = require('ffi')
 
@@ -41,7 +47,14 @@ function PolyphaseChannelizerBlock:instantiate(num_channels, taps, options)
     end
     self.method = (options or {}).method
     assert(self.method == nil or self.method == "gemm" or self.method == "fft", "Unsupported method (\"gemm\" or \"fft\")")
+    self.oversample = (options or {}).oversample or 1
+    assert(self.oversample == 1 or self.oversample == 2 or self.oversample == 4, "Unsupported oversample (1, 2 or 4)")
+    assert(self.oversample == 1 or self.method ~= "gemm", "oversample > 1 needs the FFT form: the GEMM (method = \"gemm\") is critically sampled only")
     self:add_type_signature({block.Input("in", types.ComplexFloat32)}, {block.Output("out", types.ComplexFloat32)})
+end
+
+function PolyphaseChannelizerBlock:get_rate()
+    return block.Block.get_rate(self) * self.oversample
 end
 
 function PolyphaseChannelizerBlock:initialize()
@@ -57,9 +70,18 @@ M.has_fft = lrhip.available and pcall(function ()
     return lrhip.lib.lrhip_pfb_channelizer_create(nil, 0, 0)
 end)
 
+-- The oversampled form, asked for in the same way (an oversample of 0 is refused before anything else is looked at).
+M.has_oversampled = lrhip.available and pcall(function ()
+    return lrhip.lib.lrhip_pfb_oversampled_create(nil, 0, 0, 0)
+end)
+
 function M.patch(Block)
     lrhip.device_block(Block, function (self)
         local k, m = self.num_channels, self.taps.length
+        if self.oversample > 1 then
+            assert(M.has_oversampled, "this liblrhip.so has no lrhip_pfb_oversampled_create (oversample = " .. self.oversample .. ")")
+            return lrhip.lib.lrhip_pfb_oversampled_create(ffi.cast("const float *", self.taps.data), m, k, self.oversample)
+        end
         local gemm_accepts = (k == 32 or k == 64) and m >= 32 and m <= 8192 and m % 32 == 0
         assert(self.method ~= "fft" or M.has_fft, "this liblrhip.so has no lrhip_pfb_channelizer_create (method = \"fft\")")
         if M.has_fft and (self.method == "fft" or (self.method == nil and not gemm_accepts)) then

@@ -46,6 +46,7 @@ lrhip_stage_t *lrhip_multiply_constant_create(float re, float im, int constant_c
 lrhip_stage_t *lrhip_upsampler_create(unsigned factor, int elem_size);
 lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels);
 lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels);
+lrhip_stage_t *lrhip_pfb_oversampled_create(const float *taps, unsigned ntaps, unsigned nchannels, unsigned oversample);
 lrhip_stage_t *lrhip_welch_create(unsigned n, const float *window, double scale, int logarithmic, int input_complex, unsigned overlap);
 long lrhip_welch_read(lrhip_stage_t *q, float *avg_host, int reset);
 lrhip_stage_t *lrhip_fmmod_create(double modulation_index);

@@ -42,6 +42,7 @@ SIGNATURES = {
     "lrhip_upsampler_create": (_vp, [C.c_uint, C.c_int]),
     "lrhip_channelizer_create": (_vp, [_fp, C.c_uint, C.c_uint]),
     "lrhip_pfb_channelizer_create": (_vp, [_fp, C.c_uint, C.c_uint]),
+    "lrhip_pfb_oversampled_create": (_vp, [_fp, C.c_uint, C.c_uint, C.c_uint]),
     "lrhip_welch_create": (_vp, [C.c_uint, _fp, C.c_double, C.c_int, C.c_int, C.c_uint]),
     "lrhip_welch_read": (C.c_long, [_vp, _fp, C.c_int]),
     "lrhip_fmmod_create": (_vp, [C.c_double]),

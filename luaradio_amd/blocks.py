@@ -333,7 +333,9 @@ class PolyphaseChannelizerBlock(Block):
     Output: frames of K ComplexFloat32 (channel c at position c), one per K inputs.
     options = {"method": "gemm" | "fft"}: "gemm" is one dense GEMM on the f32 matrix cores (K in {32, 64}, len(taps) a multiple
     of 32 up to 8192), "fft" the polyphase + FFT form (K a power of two in [8, 4096], K <= len(taps) <= min(64 K, 65536)).
-    Without a method: the GEMM where it accepts the shape, the FFT form otherwise."""
+    Without a method: the GEMM where it accepts the shape, the FFT form otherwise.
+    options["oversample"] = 2 or 4 (default 1): the hop is D = K / oversample, one frame per D inputs, each channel at oversample * rate / K,
+    and frame m * oversample is frame m of the critically sampled bank.  The FFT form only."""
     name = "PolyphaseChannelizerBlock"
 
     def instantiate(self, num_channels, taps=None, options=None):
@@ -344,10 +346,14 @@ class PolyphaseChannelizerBlock(Block):
         self.taps = types.Float32.vector_from_array(taps)
         self.method = (options or {}).get("method")
         assert self.method in (None, "gemm", "fft"), "Unsupported method \"%s\" (\"gemm\" or \"fft\")" % self.method
+        self.oversample = (options or {}).get("oversample", 1)
+        assert self.oversample in (1, 2, 4), "Unsupported oversample \"%s\" (1, 2 or 4)" % (self.oversample,)
+        if self.oversample > 1 and self.method == "gemm":
+            raise ValueError("oversample = %d needs the FFT form: the GEMM (method = \"gemm\") is critically sampled only" % self.oversample)
         self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32)])
 
     def get_rate(self):
-        return Block.get_rate(self)      # K values per K input samples; each channel runs at rate/K
+        return Block.get_rate(self) * self.oversample      # K values per K / oversample input samples; each channel runs at oversample * rate / K
 
     def gemm_accepts(self):
         """the domain of lrhip_channelizer_create"""
@@ -355,6 +361,10 @@ class PolyphaseChannelizerBlock(Block):
 
     def initialize(self):
         L = _lib.load()
+        if self.oversample > 1:
+            self._set_stage(L.lrhip_pfb_oversampled_create(_fptr(self.taps), len(self.taps), self.num_channels, self.oversample),
+                            "Creating lrhip oversampled channelizer object")
+            return
         fft = self.method == "fft" or (self.method is None and not self.gemm_accepts())
         create = L.lrhip_pfb_channelizer_create if fft else L.lrhip_channelizer_create
         self._set_stage(create(_fptr(self.taps), len(self.taps), self.num_channels), "Creating lrhip channelizer object")

@@ -480,12 +480,18 @@ lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsig
 
 lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels)
 {
-    if (const char *why = PfbChannelizerStage::refusal(taps ? ntaps : 0, nchannels)) { set_error("%s", why); return nullptr; }
+    return lrhip_pfb_oversampled_create(taps, ntaps, nchannels, 1);
+}
+
+lrhip_stage_t *lrhip_pfb_oversampled_create(const float *taps, unsigned ntaps, unsigned nchannels, unsigned oversample)
+{
+    if (const char *why = PfbChannelizerStage::refusal(taps ? ntaps : 0, nchannels, oversample)) { set_error("%s", why); return nullptr; }
     if (ensure_init()) return nullptr;
     std::unique_ptr<PfbChannelizerStage> q(new (std::nothrow) PfbChannelizerStage());
     if (!q) { set_error("out of memory"); return nullptr; }
     const int M = (int)ntaps, K = (int)nchannels;
     q->M = M; q->K = K; q->P = (M + K - 1) / K;
+    q->R = (int)oversample; q->D = K / q->R;
     while ((1 << q->log2k) < K) q->log2k++;
     q->in_size = q->out_size = 8;
     std::vector<float> tw((size_t)K);      // W_K^m = exp(-2 pi i m / K), m < K / 2 (kernels_fft.h), computed in double

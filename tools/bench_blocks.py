@@ -242,6 +242,27 @@ def main():
         blk = mk(lr.PolyphaseChannelizerBlock, [k_, lr.filter_utils.firwin_lowpass(m_, 1.0 / k_), {"method": "fft"}], True)
         pfb_row("PolyphaseChannelizer K=%d, %d taps (polyphase + FFT)" % (k_, m_),
                 [timeit(lambda: blk.process_device(xs.data_ptr(), nch, big.data_ptr(), cap), reps=10) for _ in range(4)], {})
+    # oversampled by R (hop K / R): 8 B in and 8 R B out per input sample.  The R = 1 block, the oversampled one and the streaming yardstick alternate on
+    # the same buffers; the figure of merit is bytes moved per second over the yardstick's (16 B per sample) in the same runs
+    for k_, m_ in ((64, 1024), (1024, 16384)):
+        taps_ = lr.filter_utils.firwin_lowpass(m_, 1.0 / k_)
+        crit = mk(lr.PolyphaseChannelizerBlock, [k_, taps_, {"method": "fft"}], True)
+        for r_ in (2, 4):
+            blk = mk(lr.PolyphaseChannelizerBlock, [k_, taps_, {"method": "fft", "oversample": r_}], True)
+            cap_r = blk.max_output(nch)
+            big_r = torch.empty(2 * cap_r + 64, device="cuda")
+            runs = {"crit": [], "os": [], "stream": []}
+            for _ in range(5):
+                runs["crit"].append(timeit(lambda: crit.process_device(xs.data_ptr(), nch, big_r.data_ptr(), cap_r), reps=10))
+                runs["os"].append(timeit(lambda: blk.process_device(xs.data_ptr(), nch, big_r.data_ptr(), cap_r), reps=10))
+                runs["stream"].append(timeit(lambda: mc.process_device(xs.data_ptr(), nch, big_r.data_ptr(), cap_r), reps=10))
+            for name, key, bps in (("MultiplyConstant(1.0) cf32 (streaming yardstick, alternating with K=%d R=%d)" % (k_, r_), "stream", 16),
+                                   ("PolyphaseChannelizer K=%d, %d taps (polyphase + FFT, alternating with R=%d)" % (k_, m_, r_), "crit", 16),
+                                   ("PolyphaseChannelizer K=%d, %d taps, oversample=%d (polyphase + FFT)" % (k_, m_, r_), "os", 8 * (1 + r_))):
+                ms_ = median(runs[key])
+                rows.append({"block": name, "MS/s": round(nch / ms_ / 1e3, 1), "bytes_per_sample": bps, "alg_GB/s": round(bps * nch / ms_ / 1e6, 1),
+                             "frac_8TB/s": round(bps * nch / ms_ / 1e6 / 8000, 4), "ms": round(ms_, 4), "ms_runs": [round(v, 4) for v in runs[key]],
+                             "bytes_per_s_over_streaming_yardstick": round((bps / ms_) / (16 / median(runs["stream"])), 3)})
     for r in rows:
         print(json.dumps(r))
 
