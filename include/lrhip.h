@@ -155,7 +155,17 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      that starts as N zeros), in exact fixed-point sums: bit-identical however the stream is cut.  N in
  *                                                      [1, 2^24], I in [1, 2^31], integers.  A NaN phase makes every later output NaN until reset.
  *                                                      memory() = N I.  In a chain a complextoreal right after it runs in its rotation pass (Float32 out).
- * The sampler and the clocksampler have memory() -1: chains holding them refuse time partitions. */
+ *   "preamblesampler:period=T:num_samples=N:preamble=0101..."  (preamblesampler.lua:49-138; T = floor(rate / baudrate), the preamble a string of
+ *                                                      0 / 1 characters, T and N integers) Float32 -> Float32: finds the preamble at one tap per symbol,
+ *                                                      moves on while its energy (a double sum in tap order) does not degrade, then emits N samples T
+ *                                                      apart; count data-dependent (<= ceil(n/2) + 1, <= n for T = 2).  Refused: T < 2 and N < 2 (the
+ *                                                      reference never leaves its sampling state), an empty preamble, a character other than 0 / 1, and a
+ *                                                      buffer 2^ceil_log2(T L + 1) above 2^21 samples (every T L <= 2^20 is admitted).  The carried
+ *                                                      state is the last 2^ceil_log2(T L + 1) samples and the automaton's state.
+ *   "manchesterdecoder:invert=0|1"                     (manchesterdecoder.lua:31-61) Bit -> Bit (input bytes read as & 1): a 0,1 pair gives 0 ^ invert, a
+ *                                                      1,0 pair 1 ^ invert, an equal pair is a clock slip and the newer bit stays pending; count
+ *                                                      data-dependent (<= (n + 1) / 2).
+ * The sampler, the clocksampler, the preamblesampler and the manchesterdecoder have memory() -1: chains holding them refuse time partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */
 lrhip_stage_t *lrhip_delay_create(unsigned num_samples, int elem_size);

@@ -742,3 +742,81 @@ class BinaryPhaseCorrectorBlock(Block):
 
     def process(self, x):
         return self._execute(x, np.complex64)
+
+
+# ---- the ERT receiver's blocks (luaradio_amd/csrc/stage_preamble.h)
+PREAMBLE_SAMPLER_MAX_BUFFER = 1 << 21       # PS_MAX_B: the largest circular buffer 2^ceil_log2(period * #preamble + 1) the library accepts
+
+
+def preamble_bits(preamble):
+    """a Bit vector / any sequence of 0 / 1 -> list of ints; anything else is refused (preamblesampler.lua:43-44)"""
+    if preamble is None:
+        raise AssertionError("Missing argument #2 (preamble)")
+    if isinstance(preamble, (str, bytes)) or not hasattr(preamble, "__len__"):
+        raise TypeError("Unsupported data type for argument #2 (preamble), must be a Bit vector")
+    bits = [v for v in (preamble.tolist() if isinstance(preamble, np.ndarray) else list(preamble))]
+    if any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v not in (0, 1) for v in bits):
+        raise TypeError("Unsupported data type for argument #2 (preamble), must be a Bit vector (0 / 1 values)")
+    return [int(v) for v in bits]
+
+
+def preamble_sampler_params(rate, baudrate, preamble, num_samples):
+    """(T, L, N, B) of a PreambleSamplerBlock at `rate`, with the library's create-time refusals (stage_preamble.h preamblesampler_create)"""
+    bits = preamble_bits(preamble)
+    T = int(math.floor(rate / baudrate))                 # preamblesampler.lua:50
+    if T < 2:
+        raise ValueError("preamblesampler: period must be >= 2 samples per symbol (got %d)" % T)
+    if int(num_samples) != num_samples or num_samples < 2:
+        raise ValueError("preamblesampler: num_samples must be an integer >= 2 (got %r)" % (num_samples,))
+    if not bits:
+        raise ValueError("preamblesampler: the preamble is empty")
+    B = 1
+    while B < T * len(bits) + 1:                         # 2^ceil_log2(T L + 1), preamblesampler.lua:52
+        B *= 2
+    if B > PREAMBLE_SAMPLER_MAX_BUFFER:
+        raise ValueError("preamblesampler: period * preamble length = %d needs a buffer above the limit of %d samples"
+                         % (T * len(bits), PREAMBLE_SAMPLER_MAX_BUFFER))
+    return T, len(bits), int(num_samples), B
+
+
+class PreambleSamplerBlock(Block):
+    """radio/blocks/signal/preamblesampler.lua. PreambleSamplerBlock(baudrate, preamble, num_samples): Float32 -> Float32.  Finds the
+    preamble (a Bit vector) at one tap per symbol, moves on while the preamble's energy does not degrade, then emits num_samples samples one
+    symbol apart.  The output count depends on the data."""
+    name = "PreambleSamplerBlock"
+
+    def instantiate(self, baudrate, preamble, num_samples):
+        assert baudrate is not None, "Missing argument #1 (baudrate)"
+        assert preamble is not None, "Missing argument #2 (preamble)"
+        assert num_samples is not None, "Missing argument #3 (frame length)"
+        self.baudrate, self.preamble, self.num_samples = baudrate, preamble_bits(preamble), num_samples
+        self.add_type_signature([Input("in", types.Float32)], [Output("out", types.Float32)])
+
+    def op(self):
+        T, _, N, _ = preamble_sampler_params(self.get_rate(), self.baudrate, self.preamble, self.num_samples)
+        return "preamblesampler:period=%d:num_samples=%d:preamble=%s" % (T, N, "".join(map(str, self.preamble)))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip preamblesampler object")
+
+    def process(self, x):
+        return self._execute(x, np.float32)
+
+
+class ManchesterDecoderBlock(Block):
+    """radio/blocks/signal/manchesterdecoder.lua. ManchesterDecoderBlock([invert=false]): Bit -> Bit, one output per 0,1 (0) or 1,0 (1) pair;
+    an equal pair is a clock slip and the newer bit stays pending.  The output count depends on the data."""
+    name = "ManchesterDecoderBlock"
+
+    def instantiate(self, invert=False):
+        self.invert = bool(invert)
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.Bit)])
+
+    def op(self):
+        return "manchesterdecoder:invert=%d" % int(self.invert)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip manchesterdecoder object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)

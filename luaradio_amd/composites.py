@@ -498,3 +498,40 @@ def bpsk31_receiver(rate):
     baudrate = 31.25
     return _receiver([B.LowpassFilterBlock(128, 100), B.RootRaisedCosineFilterBlock(101, 1, baudrate), B.BinaryPhaseCorrectorBlock(50),
                       B.ComplexToRealBlock(), B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)], rate)
+
+
+# The preambles and frame lengths (in bits) of the three ERT protocols, as their framers define them
+IDM_PREAMBLE = (0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 1, 0, 0, 0, 1, 0, 1, 1, 0, 1, 0, 1, 0, 0, 0, 1, 1)     # radio/blocks/protocol/idmframer.lua:59
+IDM_FRAME_LEN = 736                                                                                              # idmframer.lua:60
+SCM_PREAMBLE = (1, 1, 1, 1, 1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 1, 1, 0, 0, 0, 0, 0)                                      # radio/blocks/protocol/scmframer.lua:47
+SCM_FRAME_LEN = 96                                                                                               # scmframer.lua:48
+SCM_PLUS_PREAMBLE = (0, 0, 0, 1, 0, 1, 1, 0, 1, 0, 1, 0, 0, 0, 1, 1)                                               # radio/blocks/protocol/scmplusframer.lua:45
+SCM_PLUS_FRAME_LEN = 128                                                                                         # scmplusframer.lua:46
+ERT_PROTOCOLS = {"idm": (IDM_PREAMBLE, IDM_FRAME_LEN), "scm": (SCM_PREAMBLE, SCM_FRAME_LEN), "scm+": (SCM_PLUS_PREAMBLE, SCM_PLUS_FRAME_LEN)}
+
+
+def ert_receiver(protocols=("idm", "scm", "scm+"), rate=None, decimation=6):
+    """The compute blocks of radio/composites/ertreceiver.lua:30-76 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`), up to the
+    Bit streams the IDM / SCM / SCM+ framers read: ComplexMagnitude -> Lowpass(128, 4 * 32768) -> Downsampler(decimation) ->
+    ManchesterMatchedFilter(32768), then per protocol PreambleSampler(16384, preamble, frame length) -> Slicer.
+    g.process(**{"in": x}) returns {protocol: bits}: each branch's slicer carries its protocol's name, so the three outputs do not meet on
+    one key."""
+    from .graph import DeviceGraph
+    assert rate is not None, "Missing argument #2 (rate)"
+    symbol_rate = 32768
+    protocols = list(protocols)
+    for protocol in protocols:
+        if protocol not in ERT_PROTOCOLS:
+            raise ValueError("Unsupported protocol \"%s\"" % (protocol,))            # ertreceiver.lua:70
+    if len(set(protocols)) != len(protocols):
+        raise ValueError("protocol listed twice in %r" % (protocols,))
+    g = DeviceGraph()
+    src = g.input("in", types.ComplexFloat32, rate)
+    matched_filter = B.ManchesterMatchedFilterBlock(symbol_rate)
+    g.connect(src, B.ComplexMagnitudeBlock(), B.LowpassFilterBlock(128, symbol_rate * 4), B.DownsamplerBlock(decimation), matched_filter)
+    for protocol in protocols:
+        preamble, frame_len = ERT_PROTOCOLS[protocol]
+        slicer = B.SlicerBlock()
+        slicer.name = protocol                     # the key of this branch in process()'s result
+        g.connect(matched_filter, B.PreambleSamplerBlock(symbol_rate / 2, preamble, frame_len), slicer)
+    return g.initialize()

@@ -29,6 +29,7 @@
 #include "kernels_interp.h"
 #include "kernels_rx.h"
 #include "kernels_digital.h"
+#include "kernels_preamble.h"
 #include "kernels_phasecorr.h"
 
 using namespace lrhip;
@@ -55,6 +56,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "chain.h"
 #include "stage_phasecorr.h"
 #include "stage_digital.h"
+#include "stage_preamble.h"
 #include "chain_plan.h"
 
 // =====================================================================================================
@@ -398,6 +400,12 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         std::map<std::string, double> kv;
         const char *c = strchr(op, ':');
         const std::string head(op, c ? (size_t)(c - op) : strlen(op));
+        // the preamble travels as a string of 0 / 1 characters, which strtod would not keep (stage_preamble.h)
+        if (head == "preamblesampler") return preamblesampler_create(op);
+        if (head == "manchesterdecoder") {
+            if (!parse_op(op, name, kv, {"invert"})) return nullptr;
+            return manchesterdecoder_create(kv, op);
+        }
         if (c || digital_unary_op(head)) {
             if (!digital_unary_op(head)) { set_error("unary: unknown operation \"%s\"", op); return nullptr; }
             if (!parse_op(op, name, kv, digital_keys(head))) return nullptr;

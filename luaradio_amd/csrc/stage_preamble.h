@@ -1,0 +1,187 @@
+// stage_preamble.h - PreambleSamplerBlock and ManchesterDecoderBlock (kernels_preamble.h), created through lrhip_unary_create
+// ("preamblesampler:period=T:num_samples=N:preamble=0101..." and "manchesterdecoder:invert=0|1").  Both have a data-dependent output count:
+// run() returns the exact count, read back from the device after the last pass (one small synchronous copy per call), and memory() = -1.
+// (part of liblrhip.so; included by lrhip.hip after stage_digital.h, one translation unit)
+#pragma once
+
+// The largest circular buffer B = 2^ceil_log2(T L + 1) a preamblesampler accepts: 2^21 samples (8 MiB of history, twice for the ping-pong),
+// which admits every T L <= 2^20.
+constexpr long long PS_MAX_B = 1ll << 21;
+
+// =====================================================================================================
+// PreambleSamplerBlock: Float32 -> Float32, data-dependent count
+// =====================================================================================================
+struct PsStage : lrhip_stage {
+    PsParams p{0, 0, 0, 0};
+    std::vector<uint32_t> pre_bits;          // the preamble, bit k of word k / 32
+    DeviceBuf pre, state, hist, scratch;     // state: two PsState; hist: two histories of B samples (ping-pong with `cur`)
+    PinnedBuf h_state;
+    int cur = 0;
+    const char *kind() const override { return "preamblesampler"; }
+    long memory() const override { return -1; }
+    int reset() override
+    {
+        cur = 0;
+        PsState s[2];
+        memset(s, 0, sizeof(s));                             // SEARCHING, preamblesampler.lua:56-59
+        if (upload(pre, pre_bits.data(), pre_bits.size() * sizeof(uint32_t)) || upload(state, s, sizeof(s))) return -1;
+        return zero_fill(hist, 2 * (size_t)p.B * sizeof(float));      // the reference's buffer starts as zeros (:52)
+    }
+    // Output 0 of a frame is emitted at sample j*, output m >= 1 at j* + m T - 1: inside a frame consecutive emissions are T - 1 (m = 0 -> 1) or
+    // T samples apart.  The last one is at s' - 1; the next frame's i* >= s' and its j* > i*, so its first emission is at s' + 1 or later: 2
+    // samples apart.  Every sample carries at most one emission, whatever the carried state, so n bounds every T >= 2; for T >= 3 emissions
+    // are at least 2 samples apart and n samples hold at most ceil(n / 2) of them (the + 1 as for the sampler).
+    unsigned long max_output(unsigned long n) const override { return p.T >= 3 ? (n + 1) / 2 + 1 : n; }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (!n) return 0;
+        const unsigned long bound = max_output(n);
+        if (cap < bound) return set_error("preamblesampler: output capacity %lu < bound %lu", cap, bound);
+        const unsigned long nt = (n + PS_TILE - 1) / PS_TILE;
+        // frames with an output inside one call: the j* of consecutive frames are at least (N - 1) T + 2 samples apart, so at most
+        // n / ((N - 1) T) + 1 of them lie inside the call, plus the frame in progress at its start
+        const unsigned long max_frames = n / ((unsigned long)(p.N - 1) * (unsigned long)p.T) + 2;
+        const size_t words = (size_t)nt * PS_WORDS * 8, o_md = words, o_tm = 2 * words, o_td = o_tm + (size_t)nt * 4,
+                     o_fr = (o_td + (size_t)nt * 4 + 15) / 16 * 16, total = o_fr + max_frames * sizeof(PsFrame);
+        if (scratch.reserve(total) || h_state.reserve(sizeof(PsState))) return -1;
+        char *sp = (char *)scratch.p;
+        unsigned long long *mask_m = (unsigned long long *)sp, *mask_d = (unsigned long long *)(sp + o_md);
+        int *tile_m = (int *)(sp + o_tm), *tile_d = (int *)(sp + o_td);
+        PsFrame *frames = (PsFrame *)(sp + o_fr);
+        const PsState *si = (const PsState *)state.p + cur;
+        PsState *so = (PsState *)state.p + (cur ^ 1);
+        const float *hi = (const float *)hist.p + (size_t)cur * (size_t)p.B;
+        float *ho = (float *)hist.p + (size_t)(cur ^ 1) * (size_t)p.B;
+        const float *x = (const float *)in_dev;
+        hipLaunchKernelGGL(ps_match_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, hi, n, p, (const uint32_t *)pre.p, mask_m, mask_d, tile_m, tile_d);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(ps_walk_kernel, dim3(1), dim3(256), 0, ctx().stream, (const unsigned long long *)mask_m, (const unsigned long long *)mask_d,
+                           (const int *)tile_m, (const int *)tile_d, nt, n, p, si, so, frames, max_frames, cap);
+        LR_LAUNCH_CHECK();
+        unsigned long grid = (unsigned long)(p.B / 64) > max_frames ? (unsigned long)(p.B / 64) : max_frames;
+        grid = grid > 2048 ? 2048 : (grid < 1 ? 1 : grid);
+        hipLaunchKernelGGL(ps_emit_kernel, dim3((unsigned)grid), dim3(64), 0, ctx().stream, x, hi, ho, n, p, (const PsState *)so, (const PsFrame *)frames,
+                           (float *)out_dev, cap);
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        // the data-dependent count: the one small read-back of this stage
+        LR_HIP(hipMemcpyAsync(h_state.p, so, sizeof(PsState), hipMemcpyDeviceToHost, ctx().stream));
+        LR_HIP(hipStreamSynchronize(ctx().stream));
+        const PsState got = *(const PsState *)h_state.p;
+        if (got.overflow || got.count > bound) return set_error("preamblesampler: %llu outputs in %llu frames exceed the bound %lu (%lu frames)", got.count, got.frames, bound, max_frames);
+        return (long)got.count;
+    }
+};
+
+// "preamblesampler:period=T:num_samples=N:preamble=0101...": T and N integers, preamble a string of 0 / 1 characters
+static lrhip_stage_t *preamblesampler_create(const char *op)
+{
+    long T = 0, N = 0;
+    std::string bits;
+    bool have_t = false, have_n = false, have_p = false;
+    const char *c = strchr(op, ':');
+    while (c) {
+        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
+        if (!eq || (next && eq > next) || eq == k) { set_error("preamblesampler: malformed parameter in \"%s\" (expected key=value)", op); return nullptr; }
+        const std::string key(k, (size_t)(eq - k)), val(eq + 1, next ? (size_t)(next - eq - 1) : strlen(eq + 1));
+        bool *have = key == "period" ? &have_t : key == "num_samples" ? &have_n : key == "preamble" ? &have_p : nullptr;
+        if (!have) { set_error("preamblesampler: unknown parameter \"%s\"", key.c_str()); return nullptr; }
+        if (*have) { set_error("preamblesampler: parameter \"%s\" given twice", key.c_str()); return nullptr; }
+        *have = true;
+        if (key == "preamble") {
+            if (val.find_first_not_of("01") != std::string::npos) { set_error("preamblesampler: preamble must be a string of 0 / 1 characters, got \"%s\"", val.c_str()); return nullptr; }
+            bits = val;
+        } else {
+            char *end = nullptr;
+            errno = 0;
+            const long v = strtol(val.c_str(), &end, 10);
+            if (val.empty() || *end || errno == ERANGE || v > 0x7fffffffl || v < -0x7fffffffl) { set_error("preamblesampler: bad value for \"%s\" in \"%s\" (an integer)", key.c_str(), op); return nullptr; }
+            (key == "period" ? T : N) = v;
+        }
+        c = next;
+    }
+    if (!have_t || !have_n || !have_p) { set_error("preamblesampler: missing parameter \"%s\" in \"%s\"", !have_t ? "period" : !have_n ? "num_samples" : "preamble", op); return nullptr; }
+    // preamblesampler.lua:108-121: with a period of 1 the offset becomes 0 and is decremented before it is tested, with one sample per frame
+    // the bit count is past num_samples before it is compared - either way the reference never leaves SAMPLING
+    if (T < 2) { set_error("preamblesampler: period must be >= 2 samples per symbol (got %ld)", T); return nullptr; }
+    if (N < 2) { set_error("preamblesampler: num_samples must be >= 2 (got %ld)", N); return nullptr; }
+    if (bits.empty()) { set_error("preamblesampler: the preamble is empty"); return nullptr; }
+    const long long TL = (long long)T * (long long)bits.size();
+    long long B = 1;
+    while (B < TL + 1 && B <= PS_MAX_B) B *= 2;                  // 2^ceil_log2(T L + 1), preamblesampler.lua:52
+    if (B > PS_MAX_B) { set_error("preamblesampler: period * preamble length = %lld needs a buffer above the limit of %lld samples", TL, PS_MAX_B); return nullptr; }
+    if (ensure_init()) return nullptr;
+    std::unique_ptr<PsStage> q(new (std::nothrow) PsStage());
+    if (!q) { set_error("out of memory"); return nullptr; }
+    q->p = PsParams{(int)T, (int)bits.size(), (int)N, B};
+    q->pre_bits.assign((bits.size() + 31) / 32, 0u);
+    for (size_t k = 0; k < bits.size(); k++)
+        if (bits[k] == '1') q->pre_bits[k >> 5] |= 1u << (k & 31);
+    q->in_size = q->out_size = 4;
+    if (q->reset()) return nullptr;
+    return q.release();
+}
+
+// =====================================================================================================
+// ManchesterDecoderBlock: Bit -> Bit, data-dependent count (at most one output per two inputs, plus the pending bit: (n + 1) / 2)
+// =====================================================================================================
+struct MdStage : lrhip_stage {
+    int invert = 0;
+    DeviceBuf state, scratch;                // state: two MdState (ping-pong)
+    PinnedBuf h_count;
+    int cur = 0;
+    const char *kind() const override { return "manchesterdecoder"; }
+    long memory() const override { return -1; }
+    int reset() override
+    {
+        cur = 0;
+        MdState s[2];
+        memset(s, 0, sizeof(s));                             // nothing pending, manchesterdecoder.lua:27
+        return upload(state, s, sizeof(s));
+    }
+    // an output consumes two inputs of its own (the pending bit and the one that completes the pair); the first may be carried: (n + 1) / 2
+    unsigned long max_output(unsigned long n) const override { return (n + 1) / 2; }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (!n) return 0;
+        const unsigned long bound = max_output(n);
+        if (cap < bound) return set_error("manchesterdecoder: output capacity %lu < bound %lu", cap, bound);
+        const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
+        const size_t o_st = nt * sizeof(MSum), o_off = (o_st + nt * 4 + 7) / 8 * 8, total = o_off + nt * 8;
+        if (scratch.reserve(total) || h_count.reserve(sizeof(unsigned long long))) return -1;
+        char *sp = (char *)scratch.p;
+        MSum *tiles = (MSum *)sp;
+        int *t_state = (int *)(sp + o_st);
+        unsigned long long *t_off = (unsigned long long *)(sp + o_off);
+        const MdState *si = (const MdState *)state.p + cur;
+        MdState *so = (MdState *)state.p + (cur ^ 1);
+        const uint8_t *x = (const uint8_t *)in_dev;
+        hipLaunchKernelGGL(md_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, tiles);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(md_carry_kernel, dim3(1), dim3(256), 0, ctx().stream, (const MSum *)tiles, nt, si, so, t_state, t_off);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(md_final_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, invert, (uint8_t *)out_dev, cap, (const int *)t_state,
+                           (const unsigned long long *)t_off);
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+        LR_HIP(hipStreamSynchronize(ctx().stream));
+        const unsigned long long got = *(const unsigned long long *)h_count.p;
+        if (got > bound) return set_error("manchesterdecoder: %llu outputs exceed the bound %lu", got, bound);
+        return (long)got;
+    }
+};
+
+static lrhip_stage_t *manchesterdecoder_create(const std::map<std::string, double> &kv, const char *op)
+{
+    auto it = kv.find("invert");
+    if (it == kv.end()) { set_error("manchesterdecoder: missing parameter \"invert\" in \"%s\"", op); return nullptr; }
+    if (it->second != 0.0 && it->second != 1.0) { set_error("manchesterdecoder: invert must be 0 or 1"); return nullptr; }
+    if (ensure_init()) return nullptr;
+    std::unique_ptr<MdStage> q(new (std::nothrow) MdStage());
+    if (!q) { set_error("out of memory"); return nullptr; }
+    q->invert = it->second != 0.0;
+    q->in_size = q->out_size = 1;
+    if (q->reset()) return nullptr;
+    return q.release();
+}

@@ -138,6 +138,35 @@ def main():
     run("IIRFilter 5 ff / 3 fb cf32", lambda: mk(lr.IIRFilterBlock, [b_iir, a_iir], True), True, 16)
     run("IIRFilter 5 ff / 3 fb f32", lambda: mk(lr.IIRFilterBlock, [b_iir, a_iir], False), False, 8)
     run("IIRFilter 3 ff / 3 fb (biquad) cf32", lambda: mk(lr.IIRFilterBlock, [b_iir[:3], a_iir], True), True, 16)
+    # the ERT receiver's sampler (kernels_preamble.h: match, walk, emit + one count read-back) at 393 216 S/s, 2^24 resident Float32 samples: on noise
+    # (the match pass leaves its tap loop after a couple of taps, no frame) and with an SCM frame every 20 000 samples; next to it the clocksampler,
+    # the other multi-pass stage with a read-back, on the same noise; then ert_receiver with all three protocols (a DeviceGraph: host vectors, the
+    # copies in and out are part of its time)
+    if not only or any(t in "PreambleSampler ClockSampler ert_receiver" for t in only):
+        from luaradio_amd import composites as comp
+        m = min(n, 1 << 24)
+        rng = np.random.default_rng(2)
+        framed = (0.1 * rng.standard_normal(m)).astype(np.float32)
+        bits = np.concatenate([np.array(comp.SCM_PREAMBLE), rng.integers(0, 2, comp.SCM_FRAME_LEN - len(comp.SCM_PREAMBLE))])
+        wave = np.repeat(np.where(bits > 0, 1.0, -1.0), 24) * np.tile(1.0 - 0.5 * np.abs(np.linspace(-1, 1, 24)), len(bits))
+        for at in range(1000, m - len(wave), 20000):
+            framed[at:at + len(wave)] = wave
+        xf = torch.from_numpy(framed).cuda()
+        for name, cls, a, x_ in (("PreambleSampler(16384, SCM_PREAMBLE, 96) @ 393216, noise", lr.PreambleSamplerBlock, [16384, comp.SCM_PREAMBLE, 96], xr[:m]),
+                                 ("PreambleSampler(16384, SCM_PREAMBLE, 96) @ 393216, a frame every 20 000 samples", lr.PreambleSamplerBlock,
+                                  [16384, comp.SCM_PREAMBLE, 96], xf),
+                                 ("ClockSampler(16384) @ 393216, noise (yardstick: multi-pass stage with a count read-back)", lr.ClockSamplerBlock, [16384], xr[:m])):
+            chn = lr.Chain([mk(cls, a, False, 393216.0)])
+            cap = chn.max_output(m)
+            got = []
+            ms = timeit(lambda: got.append(chn.process_device(x_.data_ptr(), m, out.data_ptr(), cap)))
+            rows.append({"block": name, "MS/s": round(m / ms / 1e3, 1), "alg_GB/s": round(4 * m / ms / 1e6, 1), "frac_8TB/s": round(4 * m / ms / 1e6 / 8000, 4),
+                         "ms": round(ms, 4), "TFLOP/s": None, "samples": m, "outputs": int(got[-1]), "launches": chn.last_launches})
+        gx = lr.ert_receiver(rate=2359296.0)
+        xh = xc[:2 * m].cpu().numpy().view(np.complex64)
+        ms = timeit(lambda: gx.process(**{"in": xh}), reps=3)
+        rows.append({"block": "ert_receiver(idm, scm, scm+) @ 2359296 (host vectors: copies in and out included)", "MS/s": round(m / ms / 1e3, 1), "ms": round(ms, 4),
+                     "samples": m, "launches": sum(nd.runner.last_launches for nd in gx._order if nd.runner is not None)})
     if only and not any(t in "WBFM PSD Channelizer" for t in only):
         for r in rows:
             print(json.dumps(r))
