@@ -304,7 +304,7 @@ static void fold_fixups(std::vector<lrhip_chain::Op> &ops)
     for (size_t k = 0; k + 1 < ops.size() && !no_fixup_fold; k++) {
         FirStage *prod = ops[k].built() ? dynamic_cast<FirStage *>(ops[k].stage) : nullptr;
         FirStage *cons = ops[k + 1].built() ? dynamic_cast<FirStage *>(ops[k + 1].stage) : nullptr;
-        if (prod && cons && prod->post_disc && prod->ksteps != 0 && !prod->decfft && !prod->win_cplx_ok() && cons->iir_fused && cons->win_pair_ok()) {
+        if (prod && cons && prod->post_disc && prod->form(true) == FirForm::MfmaPersistent && cons->iir_fused && cons->form(true) == FirForm::WinPair) {
             prod->defer_fixup = true;
             cons->fix_src = prod;
         }
@@ -345,8 +345,8 @@ static void fold_tuner_records(std::vector<lrhip_chain::Op> &ops)
         const int raw = raw_record_fmt(ops[k]);
         FirStage *tf = ops[k + 1].built() ? dynamic_cast<FirStage *>(ops[k + 1].stage) : nullptr;
         if (!raw || !tf) continue;
-        if (tf->post_disc || tf->pre_disc || tf->use_fft || tf->decfft || tf->fft_arith || tf->taps_complex || tf->S != 2 || tf->win_cplx_ok()) continue;
-        if (!((tf->D == 5 && tf->ksteps == 51) || (tf->ksteps == 0 && tf->D > 1 && tf->decim_lds_ok()))) continue;
+        // (narrower than the stage's own predicate on purpose: a filter that does not decimate is no Tuner / Decimator and keeps its conversion launch)
+        if (!fir_raw_records_ok(*tf, fir_knobs()) || tf->D == 1) continue;
         tf->in_fmt = raw;
         tf->fmt_stage = ops[k].stage;
         tf->in_size = ops[k].stage->in_size;

@@ -8,9 +8,6 @@
 #include <string>
 
 #include "common.h"
-#ifndef LRHIP_FIR_D1_NACC
-#define LRHIP_FIR_D1_NACC 8      /* accumulators per wave of the D = 1 Toeplitz kernel (A/B: 4 with more waves per SIMD) */
-#endif
 #include "kernels_elem.h"
 #include "kernels_fft.h"
 #include "kernels_fir.h"

@@ -1,14 +1,16 @@
 // stage_fir.h - FIRFilterBlock stage: direct Toeplitz-MFMA / overlap-save FFT / decimating kernels, fused rotator, downsampler, discriminator; fir_build()
 // (part of liblrhip.so; included by lrhip.hip in this order, one translation unit)
 #pragma once
+#include "fir_form.h"
 
 // =====================================================================================================
 // FIRFilterBlock (+ fused FrequencyTranslatorBlock in front, + fused DownsamplerBlock behind)
 // =====================================================================================================
-struct FirStage : lrhip_stage {
-    int M = 0, S = 2, taps_complex = 0;
-    unsigned D = 1;
-    bool use_fft = false;
+struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D, taps, the fused neighbours - what the choice of kernel depends on)
+    // rotator + discriminator epilogue on the persistent Toeplitz kernel: window-relative phasors (kernels_fir.h, REL) unless the environment asks for the stand-alone rotator's
+    // phasors bit for bit; A/B knob: one-wave workgroups for that kernel (every wave stages its own window, no barriers: measured equal).  Read per stage, not per process
+    FirStage() { rel_rot = !LRHIP_DISC_EPI_LDS && getenv("LRHIP_TUNER_EXACT") == nullptr;
+                 rel_nw1 = getenv("LRHIP_TUNER_NW1") != nullptr; }
     std::vector<float> taps_rev;          // host copy, reversed (firfilter.lua:234-238)
     // the taps in natural order again (what fir_build was given): M taps of 1 (real) or 2 (complex) floats
     std::vector<float> natural_taps() const
@@ -20,50 +22,31 @@ struct FirStage : lrhip_stage {
         return h;
     }
     DeviceBuf d_taps, d_atab, d_ctaps4;
-    int ksteps = 0;                       // 0 => MFMA path unavailable for this (M, D)
     int mfma_blocks_per_cu = 0;           // resident workgroups of the persistent kernel (occupancy query, cached)
     int hist_pad = 0;                     // leading pad floats in the history buffers (1 for complex taps, see launch_mfma_cc)
     DeviceBuf hist[2];
     int cur = 0;
     unsigned long index = 0;              // carried downsampler index (downsampler.lua:53)
-    bool rot = false;                     // fused rotator in front
-    // rotator + discriminator epilogue on the persistent Toeplitz kernel: window-relative phasors (kernels_fir.h, REL) unless the environment asks
-    // for the stand-alone rotator's phasors bit for bit
-    bool rel_rot = !LRHIP_DISC_EPI_LDS && getenv("LRHIP_TUNER_EXACT") == nullptr;
-    bool rel_nw1 = getenv("LRHIP_TUNER_NW1") != nullptr;      // A/B knob: one-wave workgroups for that kernel (every wave stages its own window, no barriers: measured equal)
     uint64_t rot_step = 0, count = 0;     // absolute index of the next input sample
     // overlap-save emission framing (firfilter.lua:451-485)
     long L = 0, fill = 0;
     DeviceBuf pending, work;
-    // overlap-save ARITHMETIC (fused 1024-point FFT kernel); independent of the emission framing
-    static constexpr int FFT_PART = 512;   // taps per overlap-save partition (V = 512, L = 512 of the 1024-point block)
-    bool fft_arith = false;
-    // round 3: IQFileSource's format stage (u8 / s8 / s16le records) in front of a fused Tuner is folded into it: the persistent kernel converts the records
+    static constexpr int FFT_PART = FIR_FFT_PART;
+    // round 3: IQFileSource's format stage (u8 / s8 / s16le records, in_fmt) in front of a fused Tuner is folded into it: the persistent kernel converts the records
     // on the way into LDS (kernels_fir.h FMT); the stage itself (not owned) converts for every other launch form
-    int in_fmt = 0;                       // RX_FMT_*
     lrhip_stage *fmt_stage = nullptr;
     DeviceBuf converted;
     bool raw_now = false;                 // set around core() while x holds raw records
     DeviceBuf d_fft_tables;
     DeviceBuf d_fft4k_tables;             // 513 .. 1281 taps on a ComplexFloat32 stream: the 4096-point kernel (kernels_firfft4k.h)
     DeviceBuf d_fft64_tables;             // ... and its one-wave-per-block form (kernels_firfft64.h)
-    int fft64_np = 0;                     // round 5: 1 282 .. 2 049 taps (1) / 2 050 .. 4 097 taps (2 partitions) on that form at an overlap of 2 048
-    int fft4k_V = 0, fft4k_blocks = 0;    // its overlap (768 / 1024 / 1280; 0 = not built)
-    int fft_blocks_per_cu = 0;
-    // decimating polyphase-FFT form (kernels_firdecfft.h): ComplexFloat32 stream, D >= 2, ceil(M / D) <= 32
-    bool decfft = false;
+    int fft4k_blocks = 0, fft_blocks_per_cu = 0;
     int mode_req = 0;                     // use_fft as the caller passed it (0..3), before 3 = automatic was resolved
     DeviceBuf d_dec_tables;
     int dec_blocks_per_cu = 0;
     double rot_omega = 0.0;
-    static bool decfft_supported(unsigned d, int m, int s) { return s == 2 && (d == 2 || d == 4 || d == 5 || d == 8) && (m + (int)d - 1) / (int)d <= DF_V && m >= 8; }
-    // fused FrequencyDiscriminatorBlock in front (chains): input is ComplexFloat32, the filter runs on arg(c[i] conj c[i-1])/gain
     bool hist_in_kernel = false;          // set by a launch that also wrote the next history buffer
-    bool pre_disc = false;
-    // fused FrequencyDiscriminatorBlock behind the filter (chains): ComplexFloat32 in, Float32 out (persistent MFMA kernel epilogue)
-    bool post_disc = false;
     int post_unary = 0;      // 1 + UN_CMAG / UN_CPHASE / UN_CREAL / UN_CIMAG folded into the LDS-staged decimator's store (chains: tuner -> ComplexMagnitude ...), Float32 out
-    bool can_post_unary() const { return S == 2 && D > 1 && !ksteps && decim_lds_ok() && !decfft && !pre_disc && !post_disc; }
     DeviceBuf edge;
     // fix-up of the wave-first discriminator outputs (disc_epilogue): done by fir_disc_fixup_kernel, or - defer_fixup - left to the next
     // stage of the chain, a pair-mode window filter that patches the samples as it stages them (FwcParams::fix_edge): one launch less
@@ -109,53 +92,25 @@ struct FirStage : lrhip_stage {
         return m;
     }
     void rate(unsigned long *num, unsigned long *den) const override { *num = D; *den = 1; }
-    unsigned long align() const override
-    {
-        if (iir_fused) return 2UL * 256 * 5 * D;                        // pair-mode tile: 2 x 256 lanes x 5 outputs
-        if (fft_arith) {
-            // overlap-save arithmetic: the 1024-point blocks advance by Lf samples from the start of a chunk (two blocks ride together on
-            // a Float32 stream); the same grid gives the same rounding
-            unsigned long l = 1;
-            const int nparts = (M + FFT_PART - 1) / FFT_PART;
-            for (int part = 0; part < nparts; part++) {
-                const int Mp = part + 1 < nparts ? FFT_PART : M - part * FFT_PART;
-                unsigned long a = (unsigned long)(FFTN - ((Mp - 1 + 63) / 64) * 64) * (S == 1 ? 2UL : 1UL), x = l, y = a;
-                while (y) { unsigned long t = x % y; x = y; y = t; }
-                l = l / x * a;
-            }
-            return l;
-        }
-        if (rot && post_disc && !decfft && !win_cplx_ok() && rel_rot) {
-            // tuner + discriminator on the persistent Toeplitz kernel: a tile's window is rotated relative to its first sample
-            // (kernels_fir.h, REL), so the rounding follows the tile grid, which starts with the chunk
-            const int nacc5 = getenv("LRHIP_FIR_D5_NACC") ? atoi(getenv("LRHIP_FIR_D5_NACC")) : 2;
-            if (D == 1) return (unsigned long)FirMfmaGeom<2, 1>::tile_out(LRHIP_FIR_D1_NACC);
-            if (D == 5) return 5UL * FirMfmaGeom<2, 5>::tile_out(nacc5 == 1 ? 1 : 2, ksteps == 51 && rel_nw1 ? 1 : 4);
-        }
-        return 1UL;
-    }
-
-    // MFMA steps of the 128-tap ComplexFloat32 Toeplitz filter at decimation d (fir_mfma_ksteps(128, d, 2)): the shapes with a discriminator epilogue
-    static constexpr int disc_ksteps(int d) { return (1 + 15 * d + 128 + 3) / 4; }
+    unsigned long align() const override { return fir_align(*this, fir_knobs()); }
+    // the form a launch from a sample-aligned / unaligned input pointer takes
+    const FirShape &shape() const { return *this; }
+    FirForm form(bool aligned) const { return fir_form(*this, fir_knobs(), aligned); }
+    static bool decfft_supported(unsigned d, int m, int s) { return fir_decfft_supported(d, m, s); }
+    bool hilbert_ok() const { return fir_hilbert_ok(*this); }
+    bool can_post_unary() const { return fir_can_post_unary(*this); }
+    bool can_post_disc() const { return fir_can_post_disc(*this, fir_knobs()); }
+    static bool mfma_supported_decim(unsigned d) { return fir_mfma_supported_decim(d); }
+    bool direct_io_ok() const override { return !fix_src && fir_direct_io_ok(*this, fir_knobs()); }
+    // the instantiation of the Toeplitz kernel: persistent and fully unrolled (fir_mfma_persistent names the shapes), or generic
     template <int SS, int DD, int NACC>
-    int launch_mfma(const float *x, long n, float *y, long n_out)
+    int launch_mfma(bool persistent, const float *x, long n, float *y, long n_out)
     {
-        // the shapes that matter most get the persistent, fully unrolled instantiation:
-        // M = 128 at D = 1 (36 MFMA steps, the headline) and M = 128 at D = 5 (60 steps, the WBFM tuner)
-        if constexpr (DD == 1) {
-            if (ksteps == 36) return launch_mfma_ks<SS, DD, NACC, 36>(x, n, y, n_out);     // M = 128, cf32
-            if (ksteps == 37) return launch_mfma_ks<SS, DD, NACC, 37>(x, n, y, n_out);     // M = 128, f32 (slack up to 3 samples)
-        }
-        if constexpr (DD == 5) {
-            if (ksteps == 51) return launch_mfma_ks<SS, DD, NACC, 51>(x, n, y, n_out);     // M = 128 at D = 5 (Tuner / Decimator(5))
-        }
-        // Round 5: the Tuner of an FM receiver at OTHER input rates - decimation 4, 8, 10 at 128 taps - with the discriminator epilogue (only that
-        // combination: the plain Tuner / Decimator at these decimations keep the generic kernel)
-        if constexpr (SS == 2 && (DD == 4 || DD == 8 || DD == 10)) {
-            constexpr int KSD = disc_ksteps(DD);
-            if (post_disc && rot && ksteps == KSD) return launch_mfma_ks<SS, DD, NACC, KSD>(x, n, y, n_out);
-        }
-        return launch_mfma_ks<SS, DD, NACC, 0>(x, n, y, n_out);
+        if (!persistent) return launch_mfma_ks<SS, DD, NACC, 0>(x, n, y, n_out);
+        if constexpr (DD == 1) return ksteps == 36 ? launch_mfma_ks<SS, DD, NACC, 36>(x, n, y, n_out) : launch_mfma_ks<SS, DD, NACC, 37>(x, n, y, n_out);
+        else if constexpr (DD == 5) return launch_mfma_ks<SS, DD, NACC, 51>(x, n, y, n_out);
+        else if constexpr (SS == 2 && (DD == 4 || DD == 8 || DD == 10)) return launch_mfma_ks<SS, DD, NACC, fir_disc_ksteps(DD)>(x, n, y, n_out);
+        else return set_error("internal: no persistent Toeplitz kernel at decimation %d", DD);
     }
 
     template <typename K>
@@ -196,10 +151,7 @@ struct FirStage : lrhip_stage {
         }
         // alignment slack so that the tile's first staged sample is 16-B aligned in global memory (raw records: the 4- / 8-byte word of two samples)
         const unsigned esz = raw_now ? (in_fmt == RX_FMT_S16LE ? 4u : 2u) : (unsigned)(4 * SS);
-        if (((uintptr_t)x % esz) != 0) {
-            if (rot || post_disc) return set_error("fir: fused rotator / discriminator needs a sample-aligned input pointer");
-            return launch_direct(x, n, y, n_out);
-        }
+        if (((uintptr_t)x % esz) != 0) return set_error("fir: fused rotator / discriminator needs a sample-aligned input pointer");      // (without them: the direct kernel, fir_form)
         long sample_addr = (long)((uintptr_t)x / esz);
         int q = 4 / SS;
         long v = sample_addr + (long)index - (M - 1);
@@ -216,9 +168,7 @@ struct FirStage : lrhip_stage {
             auto launch = [&](auto kern) -> int {
                 if ((mfma_blocks_per_cu = prepared_blocks(kern, lds_bytes, 64 * NW)) < 0) return -1;     // queried once per instantiation
                 long slots = (long)ctx().num_cus * mfma_blocks_per_cu;
-                // tile order: persistent grid stride (0), or runs of `rounds` consecutive tiles per workgroup in address order (LRHIP_FIR_ROUNDS, A/B)
-                static const int rounds_env = getenv("LRHIP_FIR_ROUNDS") ? atoi(getenv("LRHIP_FIR_ROUNDS")) : 0;
-                const int rounds = ntiles > slots && rounds_env > 0 ? rounds_env : 0;
+                const int rounds = ntiles > slots && fir_knobs().fir_rounds > 0 ? fir_knobs().fir_rounds : 0;      // tile order (LRHIP_FIR_ROUNDS)
                 unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
                 if (post_disc && edge.reserve((size_t)ntiles * 2 * NW * sizeof(float2))) return -1;
                 float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
@@ -302,9 +252,8 @@ struct FirStage : lrhip_stage {
         return 0;
     }
 
-    // HilbertTransformBlock in one launch: the generic Float32 Toeplitz kernel with the pair epilogue (kernels_fir.h, HILB).  y2 receives n
+    // HilbertTransformBlock in one launch (hilbert_ok): the generic Float32 Toeplitz kernel with the pair epilogue (kernels_fir.h, HILB).  y2 receives n
     // ComplexFloat32 samples (delayed input, filtered input); history / index bookkeeping is core()'s (D = 1: index stays 0)
-    bool hilbert_ok() const { return S == 1 && !taps_complex && D == 1 && ksteps > 0 && !rot && !fft_arith && !use_fft && !pre_disc && !post_disc; }
     // the window form (kernels_firwin.h hilbert_win_kernel): the reference's tap counts, taps at even distance from the centre exactly zero
     int hilb_sparse = -1, hilb_blocks = 0;
     template <int MM>
@@ -319,10 +268,9 @@ struct FirStage : lrhip_stage {
             LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, kern, 256, lds_bytes));
             hilb_blocks = nb_ < 1 ? 1 : nb_;
         }
-        static const int run_knob = getenv("LRHIP_HILBERT_RUN") ? atoi(getenv("LRHIP_HILBERT_RUN")) : 0;      // A/B knob: tiles per workgroup
         const long ntiles = (n + FWR_TILE - 1) / FWR_TILE, slots = (long)ctx().num_cus * hilb_blocks;
         long run = (ntiles + 4 * slots - 1) / (4 * slots);
-        if (run_knob > 0) run = run_knob;
+        if (fir_knobs().hilbert_run > 0) run = fir_knobs().hilbert_run;      // A/B knob: tiles per workgroup
         const unsigned grid = (unsigned)((ntiles + run - 1) / run);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float *)d_taps.p, y2, n, run,
                            (float *)hist[cur ^ 1].p + hist_pad);
@@ -338,8 +286,7 @@ struct FirStage : lrhip_stage {
             for (int j = 0; j < M && hilb_sparse; j += 2)
                 if (taps_rev[(size_t)j] != 0.0f) hilb_sparse = 0;
         }
-        static const bool no_win = getenv("LRHIP_HILBERT_MFMA") != nullptr;      // A/B knob: the matrix-core pair epilogue of round 3
-        if (hilb_sparse && !no_win && index == 0) return M == 65 ? launch_hilbert_win<65>(x, n, y2) : launch_hilbert_win<129>(x, n, y2);
+        if (hilb_sparse && !fir_knobs().hilbert_mfma && index == 0) return M == 65 ? launch_hilbert_win<65>(x, n, y2) : launch_hilbert_win<129>(x, n, y2);
         constexpr int NACC = 4;
         using G = FirMfmaGeom<1, 1>;
         constexpr int TILE_OUT = G::tile_out(NACC);
@@ -373,7 +320,7 @@ struct FirStage : lrhip_stage {
     {
         using G = FirMfmaGeom<1, DD2>;
         constexpr int TILE_OUT = G::tile_out(NACC);
-        if (((uintptr_t)x % 8) != 0) return launch_direct(x, n, y, n_out);
+        if (((uintptr_t)x % 8) != 0) return set_error("internal: unaligned input reached the complex-taps Toeplitz kernel");      // (the direct kernel's: fir_form)
         const int M2 = 2 * M;
         const long first2 = 2 * (long)index + 1, n2 = 2 * n;
         long v = (long)((uintptr_t)x / 4) + first2 - (M2 - 1);
@@ -400,7 +347,7 @@ struct FirStage : lrhip_stage {
             case 3: return launch_mfma_cc<6, 1>(x, n, y, n_out);
             case 4: return launch_mfma_cc<8, 1>(x, n, y, n_out);
             case 5: return launch_mfma_cc<10, 1>(x, n, y, n_out);
-            default: return decim_lds_ok() ? launch_decim_lds(x, n, y, n_out) : launch_direct(x, n, y, n_out);
+            default: return set_error("internal: no complex-taps Toeplitz kernel at decimation %u", D);
         }
     }
 
@@ -411,13 +358,10 @@ struct FirStage : lrhip_stage {
         const size_t lds_bytes = (size_t)f4k_lds_elems(NG) * sizeof(float2);
         auto kern = fir_fft4k_kernel<VV, NG>;
         if (!*blocks_per_cu && prepare_kernel(kern, lds_bytes, blocks_per_cu, 256 * NG)) return -1;
-        // XCD-major block order (kernels_firfft4k.h), measured on 2^26 samples, same box: 1 276 taps 0.479 -> 0.448 ms (the 31 % overlap becomes L2 hits),
-        // 768 taps equal; LRHIP_F4K_XCD_MAP=0 is the plain order
-        static const int xcd_map = getenv("LRHIP_F4K_XCD_MAP") ? atoi(getenv("LRHIP_F4K_XCD_MAP")) : 1;
         const long nblocks = (n_out + Lf - 1) / Lf, nslots = (nblocks + NG - 1) / NG, slots = (long)ctx().num_cus * *blocks_per_cu;
         const unsigned grid = (unsigned)(nslots < slots ? nslots : slots);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * NG), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft4k_tables.p, y, M, n,
-                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, xcd_map);
+                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, fir_knobs().f4k_xcd_map);      // (XCD-major block order)
         LR_LAUNCH_CHECK();
         hist_in_kernel = true;
         return 0;
@@ -431,12 +375,11 @@ struct FirStage : lrhip_stage {
         const size_t lds_bytes = (size_t)f64_lds_elems(WAVES) * sizeof(float2);
         auto kern = fir_fft64_kernel<VV, WAVES, 1, SS, HG>;
         if (prepared_blocks(kern, lds_bytes, 64 * WAVES) < 0) return -1;
-        static const int xcd_map = getenv("LRHIP_F4K_XCD_MAP") ? atoi(getenv("LRHIP_F4K_XCD_MAP")) : 1;
         // (Float32 stream: two stream blocks per transform - the kernel's block count is the number of transforms)
         const long nblocks = ((n_out + Lf - 1) / Lf + (2 - SS)) / (3 - SS), nslots = (nblocks + WAVES - 1) / WAVES;
         const unsigned grid = (unsigned)(nslots < ctx().num_cus ? nslots : ctx().num_cus);      // 108 / 158 KB of LDS: one workgroup per CU
         hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft64_tables.p, y, M, n,
-                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, xcd_map, 0L, 0);
+                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, fir_knobs().f4k_xcd_map, 0L, 0);
         LR_LAUNCH_CHECK();
         hist_in_kernel = true;
         return 0;
@@ -467,23 +410,15 @@ struct FirStage : lrhip_stage {
     int launch_fft64_v(const float *x, long n, float *y, long n_out)
     {
         if (S == 1) return launch_fft64<VV, 8, 1>(x, n, y, n_out);
-        // round 6, measured and left OFF: complex taps at eight waves per CU with H read from the global table (LRHIP_F64_HG=1) are 8-10 % SLOWER than four waves
-        // with H in the LDS (1 276 taps, 2^26 samples, three alternations on one box: 0.447 / 0.444 / 0.437 against 0.404 / 0.406 / 0.405 ms, profiles/r06_ab_hg.txt) -
-        // 64 more global loads per block in a kernel whose block is already a third memory-instruction issue
-        static const int hg_knob = getenv("LRHIP_F64_HG") ? atoi(getenv("LRHIP_F64_HG")) : 0;
-        if (taps_complex) return hg_knob ? launch_fft64<VV, 8, 2, true>(x, n, y, n_out) : launch_fft64<VV, 4>(x, n, y, n_out);
+        if (taps_complex) return fir_knobs().f64_hg ? launch_fft64<VV, 8, 2, true>(x, n, y, n_out) : launch_fft64<VV, 4>(x, n, y, n_out);
         return launch_fft64<VV, 8>(x, n, y, n_out);
     }
     template <int VV>
     int launch_fft4k(const float *x, long n, float *y, long n_out)
     {
-        // A/B knob: blocks per workgroup.  2 (512 threads, shared tables, 16 waves per CU instead of 12) measured SLOWER: 0.505 against 0.479 ms - the
-        // barriers then couple eight waves; the kernel is bound by its five workgroup barriers per block, not by occupancy (counters: VALU 27 %, LDS 42 % busy)
-        static const int ng = getenv("LRHIP_F4K_NG") ? atoi(getenv("LRHIP_F4K_NG")) : 1;
-        return ng == 2 ? launch_fft4k_ng<VV, 2>(x, n, y, n_out, &fft4k_blocks2) : launch_fft4k_ng<VV, 1>(x, n, y, n_out, &fft4k_blocks);
+        return fir_knobs().f4k_ng == 2 ? launch_fft4k_ng<VV, 2>(x, n, y, n_out, &fft4k_blocks2) : launch_fft4k_ng<VV, 1>(x, n, y, n_out, &fft4k_blocks);
     }
     // ---- partitioned overlap-save (kernels_firpols.h, round 4): 513 taps and more in one launch per 1 536 taps, ComplexFloat32 or Float32 stream
-    int pols_blocks = 0;
     template <int SS, int PP>
     int launch_pols_p(const float *x, long n, float *y, long n_out, int part0)
     {
@@ -495,10 +430,9 @@ struct FirStage : lrhip_stage {
         // and the number of runs is a whole number of rounds of (CUs x waves) where the launch is long enough
         constexpr long RPW = SS == 2 ? 1 : 2;
         const long nblocks = (n_out + POLS_HOP - 1) / POLS_HOP, per_round = (long)ctx().num_cus * POLS_WPB * RPW;
-        static const long run_env = getenv("LRHIP_POLS_RUN") ? atol(getenv("LRHIP_POLS_RUN")) : 0;      // A/B knob
         long rounds = (nblocks + per_round * 20) / (per_round * 40);
         if (rounds < 1) rounds = 1;
-        long run = run_env > 0 ? run_env : (nblocks + per_round * rounds - 1) / (per_round * rounds);
+        long run = fir_knobs().pols_run > 0 ? fir_knobs().pols_run : (nblocks + per_round * rounds - 1) / (per_round * rounds);
         if (run < 4 * (PP - 1) + 4) run = 4 * (PP - 1) + 4;
         const long nruns = (nblocks + run - 1) / run, nslots = (nruns + POLS_WPB * RPW - 1) / (POLS_WPB * RPW);
         const unsigned grid = (unsigned)(nslots < ctx().num_cus ? nslots : ctx().num_cus);
@@ -518,8 +452,7 @@ struct FirStage : lrhip_stage {
         // four partitions and more (1 537 taps up) takes FOUR per launch at eight waves per CU (three spectra, 256 registers): 4 096 taps in two launches instead
         // of three - same box, three alternations (profiles/r05_ab_pols_p4.txt): 1.4846 / 1.4822 / 1.4842 -> 1.1281 / 1.1296 / 1.1158 ms on 2^26 samples.
         // LRHIP_POLS_P=3 is the round-4 split (A/B knob).
-        static const int pmax_env = getenv("LRHIP_POLS_P") ? atoi(getenv("LRHIP_POLS_P")) : 4;
-        const int PMAX = (pmax_env == 4 && SS == 2 && nparts >= 4) ? 4 : 3;
+        const int PMAX = (fir_knobs().pols_p == 4 && SS == 2 && nparts >= 4) ? 4 : 3;
         for (int p0 = 0; p0 < nparts; p0 += PMAX) {
             const int P = nparts - p0 < PMAX ? nparts - p0 : PMAX;
             int rc;
@@ -532,62 +465,14 @@ struct FirStage : lrhip_stage {
 
     int launch_fft(const float *x, long n, float *y, long n_out)
     {
-        static const bool no_4k = getenv("LRHIP_FFT_NO_4K") != nullptr;      // A/B knob: partitions of the 1024-point kernel (round 2)
-        // more than 512 taps: the partitioned form (one launch per 1 536 taps) wherever the 4096-point kernels do not apply - Float32 streams, more than
-        // 1 281 taps - instead of one accumulating pass of the 1024-point kernel per 512 taps.  LRHIP_FFT_POLS=1 / 0 forces it on (also for 513 .. 1 281
-        // taps on a ComplexFloat32 stream) / off (A/B)
-        static const int pols_knob = getenv("LRHIP_FFT_POLS") ? atoi(getenv("LRHIP_FFT_POLS")) : -1;
-        // round 5: 1 282 .. 4 097 taps on a ComplexFloat32 stream as ONE launch of the 64 x 64 kernel at an overlap of 2 048 (two partitions above 2 049 taps) once
-        // a wave's run is long enough to pay for its warm-up block; LRHIP_F64_LONG=0 keeps the partitioned 1024-point kernel (A/B)
-        static const int long_knob = getenv("LRHIP_F64_LONG") ? atoi(getenv("LRHIP_F64_LONG")) : 1;
-        // round 6: Float32 streams (real taps) ride the same kernels, two stream blocks per transform: LRHIP_F64_F32=0 keeps the partitioned kernel for them (A/B)
-        static const int f32_knob = getenv("LRHIP_F64_F32") ? atoi(getenv("LRHIP_F64_F32")) : 1;
-        if (fft64_np && long_knob && pols_knob != 1 && !pre_disc && !post_disc && (S == 2 || f32_knob)) {
-            const long nb = (n_out + 2047) / 2048;
-            // (size sweep 2^20 .. 2^26 samples, same box: faster than the partitioned kernel at every size - 4 096 taps 0.072 / 0.106 / 0.196 / 0.575 ms against
-            // 0.188 / 0.208 / 0.243 / 1.104 at 2^20 / 2^22 / 2^24 / 2^26, 2 048 taps 0.048 against 0.093 at 2^22 - so there is no lower bound; LRHIP_F64_LONG_MIN = blocks per CU)
-            static const long long_min = getenv("LRHIP_F64_LONG_MIN") ? atol(getenv("LRHIP_F64_LONG_MIN")) : 0;
-            if (nb >= long_min * ctx().num_cus) {
-                if (S == 1) return fft64_np == 1 ? launch_fft64<2048, 8, 1>(x, n, y, n_out) : launch_fft64_long<2, 1>(x, n, y, n_out);      // (np = 2, 3, 4: two partitions per launch)
-                if (fft64_np == 1) return launch_fft64_v<2048>(x, n, y, n_out);
-                return launch_fft64_long<2>(x, n, y, n_out);
-            }
+        switch (fir_fft_form(*this, fir_knobs(), n_out, ctx().num_cus)) {
+            case FirFftForm::Long64: return fft64_np == 1 ? launch_fft64_v<2048>(x, n, y, n_out) : S == 1 ? launch_fft64_long<2, 1>(x, n, y, n_out) : launch_fft64_long<2>(x, n, y, n_out);      // (np = 2, 3, 4: two partitions per launch)
+            case FirFftForm::Pols: return S == 2 ? launch_pols<2>(x, n, y, n_out) : launch_pols<1>(x, n, y, n_out);
+            case FirFftForm::Wave64: return fft4k_V == 768 ? launch_fft64_v<768>(x, n, y, n_out) : fft4k_V == 1024 ? launch_fft64_v<1024>(x, n, y, n_out) : launch_fft64_v<1280>(x, n, y, n_out);
+            case FirFftForm::Wg4k: return fft4k_V == 768 ? launch_fft4k<768>(x, n, y, n_out) : fft4k_V == 1024 ? launch_fft4k<1024>(x, n, y, n_out) : launch_fft4k<1280>(x, n, y, n_out);
+            case FirFftForm::Pass1024: break;
         }
-        // one wave per 4096-point block (fir_fft64_kernel, one 512- / 256-thread workgroup per CU) once the launch has enough blocks per CU (below); smaller
-        // launches keep the workgroup-per-block form, which spreads over more CUs.  LRHIP_F4K_WAVE=1 / 0 forces one or the other (A/B)
-        static const int wave_knob = getenv("LRHIP_F4K_WAVE") ? atoi(getenv("LRHIP_F4K_WAVE")) : -1;
-        const long nblocks4k = fft4k_V ? (n_out + (F4K_N - fft4k_V) - 1) / (F4K_N - fft4k_V) : 0;
-        // Float32 streams (round 6, size sweep 2^18 .. 2^26 on one box, profiles/r06_f32_long_filter_sizes.txt): the wave-per-block kernel beats the partitioned
-        // one at EVERY size (1 276 taps: 0.034-0.051 against 0.064-0.071 ms up to 2^23 samples - the partitioned kernel has a 40-65 us floor) except where the
-        // launch is a little more than one round of the chip's 8 x CUs waves and the filter short (768 taps at 2^24: 2 521 transforms = 1.23 rounds, 0.070 against
-        // 0.052 ms): only that window keeps the partitioned kernel
-        const long transforms = (nblocks4k + 1) / 2, one_round = 8L * ctx().num_cus;
-        const bool f32_window = fft4k_V == 768 && transforms > one_round && 20 * transforms <= 27 * one_round;
-        // ComplexFloat32 streams: the workgroup-per-block kernel up to 20 blocks per CU (real taps; 32 with complex taps, whose wave-per-block form runs four waves per
-        // CU) - re-measured in round 6 on the same sweep: at 2^23 samples (2 521-2 979 blocks, the old bound of 8 per CU already on the wave kernel) it is 15-40 %
-        // faster (1 276 taps 0.057 against 0.067 ms, 768 taps 0.048 / 0.068, complex taps 0.057 / 0.081), at 2^24 the two cross (0.108 / 0.097, 0.091 / 0.095, 0.108 / 0.119)
-        const bool wave4k = wave_knob >= 0 ? wave_knob != 0 : S == 1 ? !f32_window : nblocks4k >= (taps_complex ? 32L : 20L) * ctx().num_cus;
-        // (a Float32 stream has no workgroup-per-block kernel: where the wave-per-block kernel is not taken it stays partitioned)
-        const bool f32_part = S == 1 && (!f32_knob || !wave4k);
-        if (M > FFT_PART && !pre_disc && !post_disc && pols_knob != 0 && (pols_knob == 1 || !fft4k_V || no_4k || f32_part))
-            return S == 2 ? launch_pols<2>(x, n, y, n_out) : launch_pols<1>(x, n, y, n_out);
-        if (fft4k_V && !no_4k && !pre_disc && !post_disc && wave4k) {
-            switch (fft4k_V) {
-                case 768: return launch_fft64_v<768>(x, n, y, n_out);
-                case 1024: return launch_fft64_v<1024>(x, n, y, n_out);
-                default: return launch_fft64_v<1280>(x, n, y, n_out);
-            }
-        }
-        if (fft4k_V && !no_4k && !pre_disc && !post_disc && S == 2) {      // (ComplexFloat32 only; a Float32 stream that gets here - LRHIP_FFT_POLS=0 - takes the per-partition passes below)
-            switch (fft4k_V) {
-                case 768: return launch_fft4k<768>(x, n, y, n_out);
-                case 1024: return launch_fft4k<1024>(x, n, y, n_out);
-                default: return launch_fft4k<1280>(x, n, y, n_out);
-            }
-        }
-        size_t lds_bytes = (size_t)FFT_LDS_ELEMS * sizeof(float2);
-        static const long lds_pad = getenv("LRHIP_FFT_LDS_PAD") ? atol(getenv("LRHIP_FFT_LDS_PAD")) : 0;      // A/B knob: unused LDS per workgroup -> fewer resident workgroups per CU
-        lds_bytes += (size_t)lds_pad;
+        const size_t lds_bytes = (size_t)FFT_LDS_ELEMS * sizeof(float2) + (size_t)fir_knobs().fft_lds_pad;
         const float *h = (const float *)hist[cur].p + hist_pad;
         hist_in_kernel = false;
         // one launch per partition of at most FFT_PART taps (a plain filter has one); partitions after the first accumulate
@@ -602,7 +487,6 @@ struct FirStage : lrhip_stage {
                 if (!fft_blocks_per_cu && prepare_kernel(kern, lds_bytes, &fft_blocks_per_cu, 64 * FFT_WPB)) return -1;
                 long slots = (long)ctx().num_cus * fft_blocks_per_cu;
                 long want = (nffts + FFT_WPB - 1) / FFT_WPB;
-                static const int rounds_env = getenv("LRHIP_FFT_ROUNDS") ? atoi(getenv("LRHIP_FFT_ROUNDS")) : -1;      // A/B knob, read once
                 // one-shot order with 8 batches per workgroup once the launch exceeds the resident slots: 316 GS/s against 263-314
                 // (run-to-run spread) for the persistent stride on 2^28 samples, same box, alternating
                 // (only when the launch is many times the resident slots: a 2^26-sample chain's 1/5-rate audio filter, 1 873 workgroups
@@ -611,7 +495,7 @@ struct FirStage : lrhip_stage {
                 // now the faster order at every size - 2^26 samples 0.2155 against 0.2368 ms, 2^27 0.4199 / 0.4357, 2^28 0.8359 / 0.8412 and 0.8591 / 0.8646; the
                 // Float32 and complex-taps filters at 2^26 gain 9 % - a launch of 8-batch workgroups ends with a ragged last round that the one-block stride
                 // does not have.  The one-shot order stays as LRHIP_FFT_ROUNDS=8.
-                int rounds = rounds_env >= 0 ? rounds_env : 0;
+                int rounds = fir_knobs().fft_rounds >= 0 ? fir_knobs().fft_rounds : 0;
                 if (want <= slots) rounds = 0;
                 unsigned grid = rounds > 0 ? (unsigned)((want + rounds - 1) / rounds) : (unsigned)(want < slots ? want : slots);
                 // input / output in HOST memory (host_execute's direct mode, chain.h): a short persistent grid, so that the reads of one block and the writes of
@@ -620,9 +504,8 @@ struct FirStage : lrhip_stage {
                 // tapered tail of the one-shot order (kernels_firfft.h): the last three "waves" of workgroups own rounds/2, rounds/4, rounds/8 batches
                 // (measured equal on 2^28 samples, same box: 0.865-0.878 ms with, 0.860-0.867 without - the ~45 us fixed cost the size sweep shows is not
                 // the tail of long workgroups; opt-in, LRHIP_FFT_TAPER=1)
-                static const bool use_taper = getenv("LRHIP_FFT_TAPER") != nullptr && atoi(getenv("LRHIP_FFT_TAPER")) > 0;      // A/B knob
                 int n_full = 0, taper = 0;
-                if (rounds >= 2 && use_taper) {
+                if (rounds >= 2 && fir_knobs().fft_taper) {
                     const long r1 = rounds / 2, r2 = rounds / 4 > 0 ? rounds / 4 : 1, r3 = rounds / 8 > 0 ? rounds / 8 : 1;
                     const long tail_b = slots * (r1 + r2 + r3);
                     if (want > 2 * tail_b) {
@@ -684,20 +567,12 @@ struct FirStage : lrhip_stage {
         return 0;
     }
 
-    // decimations without a Toeplitz instantiation (and taps too long for its LDS table): LDS-staged one-output-per-thread kernel
-    bool decim_lds_ok() const { return !fft_arith && !use_fft && M + 255 <= DECIM_SPAN_MAX && !(taps_complex && rot); }
+    // decimations without a Toeplitz instantiation (and taps too long for its LDS table): LDS-staged one-output-per-thread kernel, first or second form (decim_lds2_ok)
     int decim_blocks_per_cu = 0;
-    // round 5: the second form (kernels_firdecim.h) for a ComplexFloat32 stream and real taps; LRHIP_DECIM_V1=1 keeps the first
-    bool decim_lds2_ok() const
+    int launch_decim_lds(bool v2, const float *x, long n, float *y, long n_out)
     {
-        static const bool v1_env = getenv("LRHIP_DECIM_V1") != nullptr;
-        return !v1_env && S == 2 && !taps_complex && D >= 2 && M + 255 <= DECIM2_SPAN_MAX;
-    }
-    int launch_decim_lds(const float *x, long n, float *y, long n_out)
-    {
-        const bool v2 = decim_lds2_ok();
         // staged samples per tile: the kernel's registers allow DECIM_SPAN_MAX; LRHIP_DECIM_SPAN (A/B) asks for less = smaller tiles, more workgroups per CU
-        static const long span_env = getenv("LRHIP_DECIM_SPAN") ? atol(getenv("LRHIP_DECIM_SPAN")) : 0;
+        const long span_env = fir_knobs().decim_span;
         const long span_cap = v2 ? DECIM2_SPAN_MAX : DECIM_SPAN_MAX;
         const long span_max = span_env >= 512 && span_env < span_cap && span_env >= M + 64 ? span_env : span_cap;
         const int dsc = post_disc ? 1 : 0;       // discriminator epilogue (second form only): OW counts the stored outputs, every tile computes one more in front
@@ -713,8 +588,7 @@ struct FirStage : lrhip_stage {
         auto go = [&](auto kern) -> int {
             if ((decim_blocks_per_cu = prepared_blocks(kern, lds_bytes)) < 0) return -1;
             long slots = (long)ctx().num_cus * decim_blocks_per_cu;
-            static const int rounds_env = getenv("LRHIP_DECIM_ROUNDS") ? atoi(getenv("LRHIP_DECIM_ROUNDS")) : 0;     // A/B: runs of consecutive tiles, address order
-            const int rounds = ntiles > slots && rounds_env > 0 ? rounds_env : 0;
+            const int rounds = ntiles > slots && fir_knobs().decim_rounds > 0 ? fir_knobs().decim_rounds : 0;
             unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index, (long)D, OW,
                                ntiles, rot ? rot_step : (uint64_t)0, rot ? count : (uint64_t)0, ho, post_unary, rounds);
@@ -724,8 +598,7 @@ struct FirStage : lrhip_stage {
         auto go2 = [&](auto kern) -> int {
             if ((decim_blocks_per_cu = prepared_blocks(kern, lds_bytes)) < 0) return -1;
             long slots = (long)ctx().num_cus * decim_blocks_per_cu;
-            static const int rounds_env = getenv("LRHIP_DECIM_ROUNDS") ? atoi(getenv("LRHIP_DECIM_ROUNDS")) : 0;
-            const int rounds = ntiles > slots && rounds_env > 0 ? rounds_env : 0;
+            const int rounds = ntiles > slots && fir_knobs().decim_rounds > 0 ? fir_knobs().decim_rounds : 0;
             unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
             float2 *dp = (float2 *)disc_prev.p;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index, (long)D, OW,
@@ -781,11 +654,10 @@ struct FirStage : lrhip_stage {
         auto go = [&](auto kern) -> int {
             if (!dec_blocks_per_cu && prepare_kernel(kern, lds_bytes, &dec_blocks_per_cu)) return -1;
             const long nquads = (pr.nblocks + 3) / 4, slots = (long)ctx().num_cus * dec_blocks_per_cu;
-            static const int rounds_env = getenv("LRHIP_DECFFT_ROUNDS") ? atoi(getenv("LRHIP_DECFFT_ROUNDS")) : 0;      // A/B knob, read once
             // one-shot order (common.h grid_for): workgroups of 4 waves x `rounds` consecutive quads, handed out in address order.  More
             // quads per wave amortise the table load and the first (unhidden) window request; same-box A/B at 2^26 samples:
             // rounds 1 / 2 / 4 = 0.171 / 0.167 / 0.164 ms
-            int rounds = rounds_env > 0 ? rounds_env : (nquads >= 16 * slots ? 4 : nquads >= 8 * slots ? 2 : 1);
+            int rounds = fir_knobs().decfft_rounds > 0 ? fir_knobs().decfft_rounds : (nquads >= 16 * slots ? 4 : nquads >= 8 * slots ? 2 : 1);
             pr.rounds = rounds;
             const long wgs = (nquads + 4L * rounds - 1) / (4L * rounds);
             float2 *dp = (float2 *)disc_prev.p;
@@ -799,15 +671,6 @@ struct FirStage : lrhip_stage {
         LR_LAUNCH_CHECK();
         if (post_disc) disc_cur ^= 1;
         return 0;
-    }
-    int launch_decfft(const float *x, long n, float *y, long n_out)
-    {
-        switch (D) {
-            case 2: return launch_decfft_d<2>(x, n, y, n_out);
-            case 4: return launch_decfft_d<4>(x, n, y, n_out);
-            case 5: return launch_decfft_d<5>(x, n, y, n_out);
-            default: return launch_decfft_d<8>(x, n, y, n_out);
-        }
     }
 
     int launch_direct(const float *x, long n, float *y, long n_out)
@@ -825,16 +688,7 @@ struct FirStage : lrhip_stage {
         return 0;
     }
 
-    // Float32 stream at D = 1 on the register-window kernel (kernels_firwin.h): every issued packed FMA is useful work,
-    // against 89 % for the Toeplitz product
     int win_blocks_per_cu = 0;
-    bool win_real_ok() const
-    {
-        // opt-in (LRHIP_FIR_WIN_REAL=1): 128 taps on 2^26 Float32 samples run at 0.25 ms here against 0.19 ms on the Toeplitz-MFMA kernel
-        // (same box) - at D = 1 the Toeplitz product wastes only 11 % of its MACs and keeps more waves resident
-        static const bool on = getenv("LRHIP_FIR_WIN_REAL") != nullptr && getenv("LRHIP_NO_FIR_WIN") == nullptr;
-        return on && S == 1 && !taps_complex && D == 1 && !rot && !pre_disc && !post_disc && !fft_arith && (M == 32 || M == 64 || M == 128);
-    }
     template <int MM, bool ONESHOT = false>
     int launch_win_real_m(const float *x, long n, float *y)
     {
@@ -855,40 +709,17 @@ struct FirStage : lrhip_stage {
         hist_in_kernel = pr.hist_out != nullptr;
         return 0;
     }
-    int launch_win_real(const float *x, long n, float *y)
-    {
-        return M == 32 ? launch_win_real_m<32>(x, n, y) : M == 64 ? launch_win_real_m<64>(x, n, y) : launch_win_real_m<128>(x, n, y);
-    }
-
-    // ComplexFloat32 stream with decimation (Decimator / Tuner [+ discriminator]) and the decimating Float32 filter with a fused
-    // first-order recurrence, on the register-window kernel (kernels_firwin2.h)
-    int winc_blocks_per_cu = 0;
-    bool iir_fused = false;               // pair mode: y[k] = iir_b0 v[k] + iir_na1 y[k-1] behind the filter
+    int winc_blocks_per_cu = 0;           // register-window kernel of kernels_firwin2.h (fir_win_cplx_ok, fir_win_pair_ok, fir_win_short_ok)
     float iir_b0 = 1.f, iir_na1 = 0.f, iir_na1_lo = 0.f;
     int iir_warm = 1;
     DeviceBuf d_iir_ptab, iir_state[2];
     int iir_cur = 0;
-    static bool win_off()
-    {
-        static const bool off = getenv("LRHIP_NO_FIR_WIN") != nullptr;      // A/B knob
-        return off;
-    }
-    // the ComplexFloat32 form is opt-in (LRHIP_FIR_WIN_CPLX=1): same-box A/B on the WBFM tuner + discriminator, 2^26 samples: 0.204 ms against
-    // 0.150 ms + 0.005 ms (fix-up) for the Toeplitz-MFMA kernel - both are bound by the shared MFMA / VALU datapath (rocprofv3: 1 250 VALU
-    // instructions per wave and 6 360-sample tile, 640 of them the filter), and the Toeplitz kernel keeps 3 workgroups per CU resident against 2
-    static bool win_cplx_on()
-    {
-        static const bool on = getenv("LRHIP_FIR_WIN_CPLX") != nullptr;
-        return on;
-    }
-    bool win_cplx_ok() const { return win_cplx_on() && !win_off() && S == 2 && !taps_complex && D == 5 && M == 128 && !fft_arith && !use_fft && !decfft && !pre_disc; }
-    bool win_pair_ok() const { return !win_off() && S == 1 && !taps_complex && D == 5 && M == 136 && !fft_arith && !use_fft && !rot && !pre_disc && !post_disc; }
     // first-order recurrence behind the pair-mode filter: needs |a1|^(320 w) < 1e-12 for the in-launch warm-up (w waves of 64 lanes x 5 outputs)
     // The pole q (a double: p^D of the polyphase identity) is carried as a Float32 pair hi + lo: rounded to one Float32 its relative error of
     // 2^-24 moves the DC gain by 2^-24 q / (1 - q), which for a slow filter is far above the 1e-6 parity bar of the recurrence it replaces.
     int fuse_iir1(double b0, double q)
     {
-        if (!win_pair_ok()) return -1;
+        if (!fir_win_pair_ok(*this, fir_knobs())) return -1;
         const double a1 = -q, p = std::fabs(q);
         int w = 0;
         for (int c = 1; c <= 4 && !w; c *= 2)
@@ -901,17 +732,6 @@ struct FirStage : lrhip_stage {
         if (upload(d_iir_ptab, ptab.data(), ptab.size() * sizeof(float))) return -1;
         iir_fused = true; iir_b0 = (float)b0; iir_na1 = (float)q; iir_na1_lo = (float)(q - (double)iir_na1); iir_warm = w;
         return reset();
-    }
-    // short ComplexFloat32-taps filters at D = 1 (the reference suite's 16-complex-taps entry): 2 M packed FMAs per output on the window kernel,
-    // a streaming problem like the real-taps case (the two-Toeplitz-filter form pays 2 x 2 M taps in fixed 16-output blocks)
-    bool win_short_c_ok() const
-    {
-        static const bool off = getenv("LRHIP_NO_FIR_WIN_SHORT") != nullptr;      // A/B knob
-        return !off && !win_off() && S == 2 && taps_complex && D == 1 && (M == 16 || M == 32) && d_ctaps4.p && !rot && !fft_arith && !use_fft && !pre_disc && !post_disc;
-    }
-    int launch_win_short_c(const float *x, long n, float *y, long n_out)
-    {
-        return M == 16 ? launch_win_cplx_m<16, FWC_CTAPS, 1, true>(x, n, y, n_out) : launch_win_cplx_m<32, FWC_CTAPS, 1, true>(x, n, y, n_out);
     }
     template <int MM, int MODE, int DD = 5, bool ONESHOT = false>
     int launch_win_cplx_m(const float *x, long n, float *y, long n_out)
@@ -946,14 +766,12 @@ struct FirStage : lrhip_stage {
                 fix_src->fix_ready = false;
             }
             pr.run = (pr.ntiles + slots - 1) / slots;
-            static const long tail_run_env = getenv("LRHIP_TAIL_RUN") ? atol(getenv("LRHIP_TAIL_RUN")) : 0;      // A/B knob, read once
-            if (tail_run_env > 0) pr.run = tail_run_env;
+            if (fir_knobs().tail_run > 0) pr.run = fir_knobs().tail_run;
             grid = (unsigned)((pr.ntiles + pr.run - 1) / pr.run);
         } else {
             pr.warm_waves = 4; pr.run = 1;
             // ONESHOT: a workgroup per tile, handed out in address order (short filters are a streaming problem: common.h grid_for)
-            static const bool oneshot_env = getenv("LRHIP_FIR_WIN_ONESHOT") != nullptr;      // A/B knob
-            grid = (unsigned)((ONESHOT || oneshot_env || pr.ntiles < slots) ? pr.ntiles : slots);
+            grid = (unsigned)((ONESHOT || fir_knobs().win_oneshot || pr.ntiles < slots) ? pr.ntiles : slots);
         }
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, pr);
         LR_LAUNCH_CHECK();
@@ -967,27 +785,6 @@ struct FirStage : lrhip_stage {
         if (post_disc) return rot ? launch_win_cplx_m<128, FWC_ROT | FWC_DISC>(x, n, y, n_out) : launch_win_cplx_m<128, FWC_DISC>(x, n, y, n_out);
         return rot ? launch_win_cplx_m<128, FWC_ROT>(x, n, y, n_out) : launch_win_cplx_m<128, 0>(x, n, y, n_out);
     }
-    // short filters on the ComplexFloat32 stream at D = 1 (the reference suite's 16-tap entries): at 16 taps the filter is 16 packed FMAs per
-    // output - nothing against its 16 B of traffic - and the Toeplitz product pays its fixed 16-output blocks (K = 15 + 16, half of it zeros).
-    // One-shot window kernel, same box, 2^26 samples: 16 taps 0.175 against 0.222 ms (6.1 TB/s = the copy yardstick), 32 taps 0.233 / 0.260,
-    // 64 taps 0.301 / 0.326 (there the overlap-save kernel, 0.221, is what `automatic` picks)
-    bool win_short_ok() const
-    {
-        static const bool off = getenv("LRHIP_NO_FIR_WIN_SHORT") != nullptr;      // A/B knob
-        return !off && !win_off() && S == 2 && !taps_complex && D == 1 && (M == 16 || M == 32 || M == 64) && !rot && !fft_arith && !use_fft && !pre_disc && !post_disc;
-    }
-    int launch_win_short(const float *x, long n, float *y, long n_out)
-    {
-        return M == 16 ? launch_win_cplx_m<16, 0, 1, true>(x, n, y, n_out) : M == 32 ? launch_win_cplx_m<32, 0, 1, true>(x, n, y, n_out)
-                                                                            : launch_win_cplx_m<64, 0, 1, true>(x, n, y, n_out);
-    }
-    // (the Float32-stream window kernel was measured the same way and lost: 0.153 / 0.150 ms against 0.136 / 0.136 for the Toeplitz kernel at 16 / 32 taps;
-    // what wins there is the plain streaming form, fir_short_real_kernel: four outputs per thread, loads shared through L1)
-    bool short_real_ok() const
-    {
-        static const bool off = getenv("LRHIP_NO_FIR_WIN_SHORT") != nullptr;
-        return !off && S == 1 && !taps_complex && D == 1 && (M == 16 || M == 32) && !rot && !fft_arith && !use_fft && !pre_disc && !post_disc;
-    }
     int launch_short_real(const float *x, long n, float *y)
     {
         const float *h = (const float *)hist[cur].p + hist_pad, *t = (const float *)d_taps.p;
@@ -999,58 +796,22 @@ struct FirStage : lrhip_stage {
         hist_in_kernel = ho != nullptr;
         return 0;
     }
-    int launch_win_pair(const float *x, long n, float *y, long n_out)
-    {
-        return iir_fused ? launch_win_cplx_m<136, FWC_PAIR | FWC_IIR>(x, n, y, n_out) : launch_win_cplx_m<136, FWC_PAIR>(x, n, y, n_out);
-    }
 
     template <int SS>
-    int dispatch_mfma(const float *x, long n, float *y, long n_out)
+    int dispatch_mfma(bool persistent, const float *x, long n, float *y, long n_out)
     {
         switch (D) {
-            case 1: return launch_mfma<SS, 1, LRHIP_FIR_D1_NACC>(x, n, y, n_out);
-            case 2: return launch_mfma<SS, 2, 4>(x, n, y, n_out);
-            case 3: return launch_mfma<SS, 3, 2>(x, n, y, n_out);
-            case 4: return launch_mfma<SS, 4, 2>(x, n, y, n_out);
-            case 5: {
-                static const int nacc5 = getenv("LRHIP_FIR_D5_NACC") ? atoi(getenv("LRHIP_FIR_D5_NACC")) : 2;      // A/B knob: accumulators per wave at D = 5
-                return nacc5 == 1 ? launch_mfma<SS, 5, 1>(x, n, y, n_out) : launch_mfma<SS, 5, 2>(x, n, y, n_out);
-            }
-            case 6: return launch_mfma<SS, 6, 1>(x, n, y, n_out);
-            case 7: return launch_mfma<SS, 7, 1>(x, n, y, n_out);
-            case 8: return launch_mfma<SS, 8, 1>(x, n, y, n_out);
-            case 10: return launch_mfma<SS, 10, 1>(x, n, y, n_out);
-            default: return decim_lds_ok() ? launch_decim_lds(x, n, y, n_out) : launch_direct(x, n, y, n_out);
+            case 1: return launch_mfma<SS, 1, LRHIP_FIR_D1_NACC>(persistent, x, n, y, n_out);
+            case 2: return launch_mfma<SS, 2, 4>(persistent, x, n, y, n_out);
+            case 3: return launch_mfma<SS, 3, 2>(persistent, x, n, y, n_out);
+            case 4: return launch_mfma<SS, 4, 2>(persistent, x, n, y, n_out);
+            case 5: return fir_knobs().d5_nacc == 1 ? launch_mfma<SS, 5, 1>(persistent, x, n, y, n_out) : launch_mfma<SS, 5, 2>(persistent, x, n, y, n_out);
+            case 6: return launch_mfma<SS, 6, 1>(persistent, x, n, y, n_out);
+            case 7: return launch_mfma<SS, 7, 1>(persistent, x, n, y, n_out);
+            case 8: return launch_mfma<SS, 8, 1>(persistent, x, n, y, n_out);
+            case 10: return launch_mfma<SS, 10, 1>(persistent, x, n, y, n_out);
+            default: return set_error("internal: no Toeplitz kernel at decimation %u", D);
         }
-    }
-
-    static bool mfma_supported_decim(unsigned d) { return (d >= 1 && d <= 8) || d == 10; }
-    // the discriminator epilogue exists for the persistent instantiations of the complex-stream, real-taps kernel
-    // (round 5: and for the Tuner - rotator fused - at decimation 4, 8, 10 with 128 taps: FM receivers at other input rates)
-    bool can_post_disc() const
-    {
-        if (decfft || win_cplx_ok()) return true;
-        if (!(S == 2 && !taps_complex && !fft_arith && !use_fft)) return false;
-        if ((D == 1 && ksteps == 36) || (D == 5 && ksteps == 51)) return true;
-        // round 5: the second LDS-staged decimator form (kernels_firdecim.h) has the epilogue at every decimation it takes - Tuner(.., 50) / (.., 80) +
-        // FrequencyDiscriminator of rtlsdr_nbfm.lua, rtlsdr_pocsag.lua, rtlsdr_ax25.lua: one launch less, the ComplexFloat32 tuner output never reaches HBM
-        static const bool no_lds_disc = getenv("LRHIP_NO_DISC_EPI_LDS") != nullptr;      // A/B knob
-        if (!no_lds_disc && ksteps == 0 && D > 1 && decim_lds_ok() && decim_lds2_ok()) return true;
-        static const bool off = getenv("LRHIP_NO_DISC_EPI_OTHER_D") != nullptr;      // A/B knob: the round-4 behaviour
-        return !off && rot && (D == 4 || D == 8 || D == 10) && ksteps == disc_ksteps(D);
-    }
-
-    // round 5 (host_execute's direct mode, the ring's in-place input): the forms that stage their input through LDS ONCE in one launch and never read
-    // their output back - overlap-save in one launch, the Toeplitz kernels, the LDS-staged decimators, the polyphase-FFT decimator.  Not the last-resort
-    // direct kernel (M global reads per output), the multi-launch partitioned filters (they accumulate into y), the opt-in window kernels
-    bool direct_io_ok() const override
-    {
-        if (pre_disc || fix_src) return false;
-        if (use_fft) return false;            // the reference's block-emission framing: run() copies x into `pending` / `work` first (a second pass, device-to-device)
-        if (decfft) return true;
-        if (fft_arith) return M <= FFT_PART || (S == 2 && (fft4k_V || (fft64_np && fft64_np <= 2)));      // (4 098 taps and more: the second launch re-reads y)
-        if (win_real_ok() || win_cplx_ok() || short_real_ok()) return false;
-        return ksteps != 0 || (D > 1 && decim_lds_ok());
     }
 
     // filter n inputs (device), emit the retained outputs; advances history / index / count
@@ -1071,17 +832,22 @@ struct FirStage : lrhip_stage {
             fix_src->fix_ready = false;
         }
         if (n_out > 0) {
-            int rc = (decfft && ((uintptr_t)x & 7) == 0) ? launch_decfft(x, n, y, n_out)
-                     : fft_arith ? launch_fft(x, n, y, n_out)
-                     : win_real_ok() ? launch_win_real(x, n, y)
-                     : win_cplx_ok() ? launch_win_cplx(x, n, y, n_out)
-                     : win_short_ok() ? launch_win_short(x, n, y, n_out)
-                     : win_short_c_ok() ? launch_win_short_c(x, n, y, n_out)
-                     : short_real_ok() ? launch_short_real(x, n, y)
-                     : win_pair_ok() ? launch_win_pair(x, n, y, n_out)
-                     : !ksteps ? (decim_lds_ok() ? launch_decim_lds(x, n, y, n_out) : launch_direct(x, n, y, n_out))
-                     : taps_complex ? dispatch_mfma_cc(x, n, y, n_out)
-                     : S == 1 ? dispatch_mfma<1>(x, n, y, n_out) : dispatch_mfma<2>(x, n, y, n_out);
+            const FirForm f = form((uintptr_t)x % (raw_now ? (in_fmt == RX_FMT_S16LE ? 4u : 2u) : 4u * (unsigned)S) == 0);      // (aligned to the sample - raw records: the record - size?)
+            int rc = -1;
+            switch (f) {
+                case FirForm::DecFft: rc = D == 2 ? launch_decfft_d<2>(x, n, y, n_out) : D == 4 ? launch_decfft_d<4>(x, n, y, n_out) : D == 5 ? launch_decfft_d<5>(x, n, y, n_out) : launch_decfft_d<8>(x, n, y, n_out); break;
+                case FirForm::OverlapSave: rc = launch_fft(x, n, y, n_out); break;
+                case FirForm::WinReal: rc = M == 32 ? launch_win_real_m<32>(x, n, y) : M == 64 ? launch_win_real_m<64>(x, n, y) : launch_win_real_m<128>(x, n, y); break;
+                case FirForm::WinCplx: rc = launch_win_cplx(x, n, y, n_out); break;
+                case FirForm::WinShort: rc = M == 16 ? launch_win_cplx_m<16, 0, 1, true>(x, n, y, n_out) : M == 32 ? launch_win_cplx_m<32, 0, 1, true>(x, n, y, n_out) : launch_win_cplx_m<64, 0, 1, true>(x, n, y, n_out); break;
+                case FirForm::WinShortC: rc = M == 16 ? launch_win_cplx_m<16, FWC_CTAPS, 1, true>(x, n, y, n_out) : launch_win_cplx_m<32, FWC_CTAPS, 1, true>(x, n, y, n_out); break;
+                case FirForm::ShortReal: rc = launch_short_real(x, n, y); break;
+                case FirForm::WinPair: rc = iir_fused ? launch_win_cplx_m<136, FWC_PAIR | FWC_IIR>(x, n, y, n_out) : launch_win_cplx_m<136, FWC_PAIR>(x, n, y, n_out); break;
+                case FirForm::DecimLds1: case FirForm::DecimLds2: rc = launch_decim_lds(f == FirForm::DecimLds2, x, n, y, n_out); break;
+                case FirForm::Direct: rc = launch_direct(x, n, y, n_out); break;
+                case FirForm::MfmaCc: rc = dispatch_mfma_cc(x, n, y, n_out); break;
+                case FirForm::MfmaPersistent: case FirForm::MfmaGeneric: rc = S == 1 ? dispatch_mfma<1>(f == FirForm::MfmaPersistent, x, n, y, n_out) : dispatch_mfma<2>(f == FirForm::MfmaPersistent, x, n, y, n_out); break;
+            }
             if (rc) return rc;
         }
         if (pre_disc) {
@@ -1113,11 +879,7 @@ struct FirStage : lrhip_stage {
     // does this chunk reach the persistent Tuner kernel, the one with a record instantiation?  (core()'s dispatch, the D = 5 / 128-tap shape)
     bool raw_path_ok(const void *in_dev, unsigned long n_in) const
     {
-        if (!in_fmt || post_disc || pre_disc || use_fft || decfft || fft_arith || taps_complex || S != 2) return false;
-        // the two kernels with record instantiations: the persistent Toeplitz kernel (128 taps, decimation 5) and the LDS-staged decimator (no Toeplitz shape)
-        if (!((D == 5 && ksteps == 51) || (ksteps == 0 && decim_lds_ok()))) return false;
-        if (win_cplx_ok() || win_pair_ok() || win_short_ok() || win_short_c_ok() || win_real_ok() || short_real_ok()) return false;
-        if (n_in <= index) return false;                                  // no output: nothing launches, the history kernel would read x
+        if (!in_fmt || !fir_raw_records_ok(*this, fir_knobs()) || n_in <= index) return false;      // (no output: nothing launches, the history kernel would read x)
         return ((uintptr_t)in_dev % (in_fmt == RX_FMT_S16LE ? 4u : 2u)) == 0;
     }
     long run(const void *in_dev, unsigned long n_in, void *out_dev, unsigned long cap) override
@@ -1125,9 +887,8 @@ struct FirStage : lrhip_stage {
         const float *x = (const float *)in_dev;
         float *y = (float *)out_dev;
         if (in_fmt) {
-            static const bool no_raw = getenv("LRHIP_TUNER_NO_RAW") != nullptr;      // A/B knob: conversion launch first
             if (!n_in) return 0;
-            if (!no_raw && raw_path_ok(in_dev, n_in)) {
+            if (!fir_knobs().tuner_no_raw && raw_path_ok(in_dev, n_in)) {
                 raw_now = true;
                 const long rc = core(x, (long)n_in, y, cap);
                 raw_now = false;
@@ -1259,13 +1020,14 @@ static FirStage *fir_build(const float *taps, unsigned ntaps, int taps_complex, 
         }
     }
     if (taps_complex && decim == 1 && input_complex && (ntaps == 16 || ntaps == 32)) {
-        // short complex filters as a streaming kernel (launch_win_short_c): (re, im, -im, re) per reversed tap
+        // short complex filters as a streaming kernel (FirForm::WinShortC): (re, im, -im, re) per reversed tap
         std::vector<float> t4((size_t)4 * ntaps);
         for (unsigned j = 0; j < ntaps; j++) {
             const float hr = q->taps_rev[2 * j], hi = q->taps_rev[2 * j + 1];
             t4[4 * j] = hr; t4[4 * j + 1] = hi; t4[4 * j + 2] = -hi; t4[4 * j + 3] = hr;
         }
         if (upload(q->d_ctaps4, t4.data(), t4.size() * sizeof(float))) return nullptr;
+        q->ctaps4 = true;
     }
     if (taps_complex && decim <= 5) {
         // taps'_re = interleave(hr_rev, -hi_rev), taps'_im = interleave(hi_rev, hr_rev) over the float stream

@@ -56,8 +56,8 @@ struct RxStage : lrhip_stage {
 
     static bool shapes_ok(const FirStage *a, const FirStage *b)
     {
-        return a && b && b->iir_fused && pole_ok(b) && a->S == 2 && !a->taps_complex && a->D == 5 && a->M == RX_M && a->ksteps == RX_KS && a->rot && a->rel_rot && a->post_disc &&
-               !a->decfft && !a->fft_arith && !a->use_fft && !a->win_cplx_ok() && b->S == 1 && b->M == RX_MT && b->D == 5 && b->ksteps == RX_KST && b->d_atab.p && b->iir_fused && b->win_pair_ok();
+        return a && b && b->iir_fused && pole_ok(b) && a->form(true) == FirForm::MfmaPersistent && a->S == 2 && a->D == 5 && a->M == RX_M && a->ksteps == RX_KS && a->rot && a->rel_rot &&
+               a->post_disc && b->form(true) == FirForm::WinPair && b->M == RX_MT && b->ksteps == RX_KST && b->d_atab.p;
     }
 
     int prepare()

@@ -296,3 +296,20 @@ def test_fft_building_blocks_run_on_the_cpu(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
+def test_fir_kernel_form_table_on_the_cpu(tmp_path):
+    """Which kernel a FIR stage launches is decided in ONE place, luaradio_amd/csrc/fir_form.h (host-only: fir_form() for FirStage::core(), fir_fft_form()
+    for the overlap-save forms, and what align() / direct_io_ok() / raw_path_ok() answer).  tools/host_fir_form_check.hip holds a literal table
+    (shape, knobs, aligned, n_out, num_cus) -> form, derived by hand from the cascades the stage spelled out before: every form, both sides of every
+    numeric edge (tap counts, span limits, persistent step counts, blocks per CU), every knob the tests and tools set."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "host_fir_form_check")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"),
+                        "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "host_fir_form_check.hip")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
