@@ -165,6 +165,15 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *   "manchesterdecoder:invert=0|1"                     (manchesterdecoder.lua:31-61) Bit -> Bit (input bytes read as & 1): a 0,1 pair gives 0 ^ invert, a
  *                                                      1,0 pair 1 ^ invert, an equal pair is a clock slip and the newer bit stays pending; count
  *                                                      data-dependent (<= (n + 1) / 2).
+ *   "pam:period=P:bits=b:msb=0|1:table=a0,a1,..."     (pulseamplitudemodulator.lua:57-87) Bit -> Float32: b bits (a byte counts as 1 only when it equals
+ *                                                      1; msb=1: the first bit is the most significant) select one of the 2^b table entries, which is
+ *                                                      held for P output samples.  P = floor(sample_rate / symbol_rate) in 1 .. 2^30 - 1, b in 1 .. 16,
+ *                                                      integers; the table as decimal (%.9g) or hexadecimal floating-point text, read with strtod and
+ *                                                      rounded to Float32 (both forms give back the Float32 they were printed from).  A call emits
+ *                                                      floor((pending + n) / b) P samples (max_output: ceil(n / b) P) and carries the remaining < b bits;
+ *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
+ *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
+ *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
  * The sampler, the clocksampler, the preamblesampler and the manchesterdecoder have memory() -1: chains holding them refuse time partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */

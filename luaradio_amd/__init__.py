@@ -16,7 +16,8 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      FMPreemphasisFilterBlock, FloatToComplexBlock, ComplexToFloatBlock, FrequencyModulatorBlock,
                      PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
                      ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock,
-                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock)
+                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock,
+                     PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401
 from . import ipc, meters, procfanout, timeshard  # noqa: F401

@@ -820,3 +820,135 @@ class ManchesterDecoderBlock(Block):
 
     def process(self, x):
         return self._execute(x, np.uint8)
+
+
+# ---- the Bit -> sample blocks (luaradio_amd/csrc/stage_modulator.h)
+MODULATOR_MAX_BITS = 16                     # MOD_MAX_BITS: the symbol table holds at most 2^16 entries
+
+
+def _symbol_bits(count, what):
+    """log2 of `levels` / `points`, with the reference's assertion (pulseamplitudemodulator.lua:37) and the library's table limit"""
+    ok = isinstance(count, (int, float, np.integer, np.floating)) and not isinstance(count, bool) and count > 1 and int(count) == count and \
+        (int(count) & (int(count) - 1)) == 0
+    assert ok, "%s is not greater than 1 and a power of 2" % what
+    bits = int(count).bit_length() - 1
+    if bits > MODULATOR_MAX_BITS:
+        raise ValueError("%s = %d needs a symbol table above the limit of 2^%d entries" % (what, int(count), MODULATOR_MAX_BITS))
+    return bits
+
+
+def _symbol_period(symbol_rate, sample_rate):
+    period = int(math.floor(sample_rate / symbol_rate))      # pulseamplitudemodulator.lua:40: from the arguments, not from the block's rate
+    if period < 1:
+        raise ValueError("symbol period floor(sample_rate / symbol_rate) = %d is below one sample" % period)
+    return period
+
+
+def _symbol_table(custom, size, option):
+    """options.amplitudes / options.constellation: a dict or a sequence indexed by symbol value -> list of `size` entries"""
+    if isinstance(custom, dict):
+        missing = [v for v in range(size) if v not in custom]
+        if missing:
+            raise ValueError("%s has no entry for symbol value %d" % (option, missing[0]))
+        return [custom[v] for v in range(size)]
+    entries = list(custom)
+    if len(entries) < size:
+        raise ValueError("%s has no entry for symbol value %d" % (option, len(entries)))
+    return entries[:size]
+
+
+def pam_amplitudes(levels):
+    """PulseAmplitudeModulatorBlock:_build_amplitudes (pulseamplitudemodulator.lua:47-55): Gray-mapped, unit mean energy; computed in double and
+    rounded once to Float32 (:62)"""
+    scaling = math.sqrt((levels ** 2 - 1) / 3)
+    table = np.zeros(levels, np.float32)
+    for level in range(levels):
+        table[level ^ (level >> 1)] = np.float32((2 * level - levels + 1) / scaling)
+    return table
+
+
+def qam_constellation(points):
+    """QuadratureAmplitudeModulatorBlock:_build_constellation (quadratureamplitudemodulator.lua:47-67).  The integer grid point is exact in
+    ComplexFloat32; scalar_div (complexfloat32.lua:141-143) divides each component by the double scaling and rounds once to Float32."""
+    symbol_bits = int(points).bit_length() - 1
+    q_bits = symbol_bits - (symbol_bits + 1) // 2
+    i_levels, q_levels = 2 ** (symbol_bits - q_bits), 2 ** q_bits
+    scaling = math.sqrt(2 * (points - 1) / 3)
+    table = np.zeros(points, np.complex64)
+    for point in range(points):
+        i_value, q_value = point >> q_bits, point & (q_levels - 1)
+        gray = ((i_value ^ (i_value >> 1)) << q_bits) | (q_value ^ (q_value >> 1))
+        re, im = np.float32(2 * i_value - i_levels + 1), np.float32(2 * q_value - q_levels + 1)
+        table[gray] = complex(np.float32(float(re) / scaling), np.float32(float(im) / scaling))
+    return table
+
+
+class _ModulatorBlock(Block):
+    _op, _out, _count_name, _table_option = None, None, None, None
+
+    def instantiate(self, symbol_rate, sample_rate, count, options=None):
+        assert symbol_rate is not None, "Missing argument #1 (symbol_rate)"
+        assert sample_rate is not None, "Missing argument #2 (sample_rate)"
+        assert count is not None, "Missing argument #3 (%s)" % self._count_name.lower()
+        self.symbol_rate, self.sample_rate, self.options = symbol_rate, sample_rate, dict(options or {})
+        self.symbol_bits = _symbol_bits(count, self._count_name)
+        self.symbol_period = _symbol_period(symbol_rate, sample_rate)
+        msb_first = self.options.get("msb_first")
+        self.msb_first = True if msb_first is None else bool(msb_first)
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", self._out)])
+
+    def _default_table(self):
+        raise NotImplementedError
+
+    def table(self):
+        """the symbol table as the output type's vector, indexed by symbol value"""
+        custom = self.options.get(self._table_option)
+        if custom is None:
+            return self._default_table()
+        entries = _symbol_table(custom, 1 << self.symbol_bits, self._table_option)
+        if self._out is types.ComplexFloat32:
+            entries = [complex(*e) if isinstance(e, (list, tuple)) else complex(e) for e in entries]
+            return np.array([complex(np.float32(e.real), np.float32(e.imag)) for e in entries], np.complex64)
+        return np.array([np.float32(e) for e in entries], np.float32)
+
+    def op(self):
+        values = self.table().view(np.float32)
+        return "%s:period=%d:bits=%d:msb=%d:table=%s" % (self._op, self.symbol_period, self.symbol_bits, int(self.msb_first),
+                                                        ",".join("%.9g" % float(v) for v in values))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self._op)
+
+    def process(self, x):
+        return self._execute(x, self._out.dtype)
+
+
+class PulseAmplitudeModulatorBlock(_ModulatorBlock):
+    """radio/blocks/signal/pulseamplitudemodulator.lua. PulseAmplitudeModulatorBlock(symbol_rate, sample_rate, levels[, options]): Bit -> Float32.
+    log2(levels) bits make a symbol, its amplitude is held for floor(sample_rate / symbol_rate) samples; bits that do not fill a symbol wait for the
+    next call.  options: msb_first (default True), amplitudes (dict or sequence indexed by symbol value).  As in the reference the block does not
+    change the rate it reports: a rate-dependent block behind it is given the sample rate by its caller."""
+    name = "PulseAmplitudeModulatorBlock"
+    _op, _out, _count_name, _table_option = "pam", types.Float32, "Levels", "amplitudes"
+
+    def instantiate(self, symbol_rate, sample_rate, levels, options=None):
+        _ModulatorBlock.instantiate(self, symbol_rate, sample_rate, levels, options)
+        self.levels = int(levels)
+
+    def _default_table(self):
+        return pam_amplitudes(self.levels)
+
+
+class QuadratureAmplitudeModulatorBlock(_ModulatorBlock):
+    """radio/blocks/signal/quadratureamplitudemodulator.lua. QuadratureAmplitudeModulatorBlock(symbol_rate, sample_rate, points[, options]):
+    Bit -> ComplexFloat32, as the pulse amplitude modulator with a constellation.  options: msb_first (default True), constellation (dict or
+    sequence indexed by symbol value; entries complex numbers or (re, im) pairs)."""
+    name = "QuadratureAmplitudeModulatorBlock"
+    _op, _out, _count_name, _table_option = "qam", types.ComplexFloat32, "Points", "constellation"
+
+    def instantiate(self, symbol_rate, sample_rate, points, options=None):
+        _ModulatorBlock.instantiate(self, symbol_rate, sample_rate, points, options)
+        self.points = int(points)
+
+    def _default_table(self):
+        return qam_constellation(self.points)

@@ -28,6 +28,7 @@
 #include "kernels_digital.h"
 #include "kernels_preamble.h"
 #include "kernels_phasecorr.h"
+#include "kernels_modulator.h"
 
 using namespace lrhip;
 
@@ -54,6 +55,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_phasecorr.h"
 #include "stage_digital.h"
 #include "stage_preamble.h"
+#include "stage_modulator.h"
 #include "chain_plan.h"
 
 // =====================================================================================================
@@ -399,6 +401,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         const std::string head(op, c ? (size_t)(c - op) : strlen(op));
         // the preamble travels as a string of 0 / 1 characters, which strtod would not keep (stage_preamble.h)
         if (head == "preamblesampler") return preamblesampler_create(op);
+        // the modulators carry their symbol table as a list (stage_modulator.h)
+        if (head == "pam" || head == "qam") return modulator_create(op);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

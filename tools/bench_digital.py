@@ -19,7 +19,11 @@ def main():
     ap.add_argument("--log2-samples", type=int, default=26)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--modulators", action="store_true", help="only the PAM / QAM modulator rows (profiles/modulator_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators: append the rows to this file as well")
     args = ap.parse_args()
+    if args.modulators:
+        return modulator_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -96,6 +100,69 @@ def main():
     xh = xc[:m].cpu().numpy()
     ms = timed(lambda: g.process(**{"in": xh}))
     print(json.dumps({"row": "pocsag_receiver (host vectors)", "samples": m, "rate": 1e6, "ms": round(ms, 4), "MS/s": round(m / ms / 1e3, 1)}))
+
+
+def modulator_rows(args):
+    """The stand-alone modulators at 2^log2-samples OUTPUT samples (the kernels are bound by their stores), each next to a store-only pass over
+    exactly the bytes it writes (torch's fill_ on the same buffer: a yardstick for the store stream, not one of the library's kernels), the two
+    alternating three times; and QAM(4), 8 samples per symbol -> RootRaisedCosineFilterBlock(129 taps) at 2^(log2-samples - 2) output samples as a
+    Chain.  --out appends the rows to a file (profiles/modulator_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+
+    def emit(row):
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    def made(blk, in_type, rate):
+        blk.rate = rate
+        blk.differentiate([in_type])
+        blk.initialize()
+        return blk
+
+    n_out = 1 << args.log2_samples
+    for cls, count, period, out_size in [(lr.PulseAmplitudeModulatorBlock, 4, 8, 4), (lr.QuadratureAmplitudeModulatorBlock, 4, 8, 8),
+                                         (lr.PulseAmplitudeModulatorBlock, 4, 1, 4), (lr.QuadratureAmplitudeModulatorBlock, 4, 1, 8)]:
+        bits = 2 * (n_out // period)
+        x = torch.from_numpy(rng.integers(0, 2, bits).astype(np.uint8)).cuda()
+        y = torch.empty(n_out * out_size // 4, dtype=torch.float32, device="cuda")
+        blk = made(cls(1.0, float(period), count), types.Bit, 1.0)
+        ms, ms_store = [], []
+        for _ in range(3):
+            ms.append(timed(lambda: blk.process_device(x.data_ptr(), bits, y.data_ptr(), n_out)))
+            ms_store.append(timed(lambda: y.fill_(1.0)))
+        emit({"row": "%s(%d) P=%d" % (cls.name, count, period), "outputs": n_out, "ms": ms, "store_only_ms": ms_store,
+              "share_of_store_only": round(min(ms_store) / min(ms), 3), "roof_fraction": round((n_out * out_size + bits) / (min(ms) * 1e-3) / 8e12, 3)})
+    m_out, period = n_out >> 2, 8
+    bits = 2 * (m_out // period)
+    x = torch.from_numpy(rng.integers(0, 2, bits).astype(np.uint8)).cuda()
+    y = torch.empty(2 * m_out + 64, dtype=torch.float32, device="cuda")
+    chain = lr.Chain([made(lr.QuadratureAmplitudeModulatorBlock(1.0, float(period), 4), types.Bit, 1.0),
+                      made(lr.RootRaisedCosineFilterBlock(129, 0.35, 1.0), types.ComplexFloat32, float(period))])
+    cap = chain.max_output(bits)
+    ms = [timed(lambda: chain.process_device(x.data_ptr(), bits, y.data_ptr(), cap)) for _ in range(3)]
+    emit({"row": "QAM(4) P=8 -> RRC(129)", "outputs": m_out, "ms": ms, "launches": chain.last_launches, "GS/s": round(m_out / min(ms) / 1e6, 2)})
 
 
 if __name__ == "__main__":
