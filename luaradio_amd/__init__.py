@@ -17,13 +17,14 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
                      ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock,
                      BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock,
-                     PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock)
+                     PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401
 from . import ipc, meters, procfanout, timeshard  # noqa: F401
 from .graph import DeviceGraph  # noqa: F401
 from .composites import (Chain, CompositeBlock, DecimatorBlock, InterpolatorBlock, RationalResamplerBlock, TunerBlock, WBFMMonoDemodulator,  # noqa: F401
                          NBFMDemodulator, AMEnvelopeDemodulator, SSBDemodulator, SSBModulator, wbfm_mono_receiver, am_envelope_receiver,
-                         ssb_receiver, nbfm_receiver, ax25_receiver, pocsag_receiver, bpsk31_receiver, ert_receiver)
+                         ssb_receiver, nbfm_receiver, ax25_receiver, pocsag_receiver, bpsk31_receiver, ert_receiver, am_synchronous_receiver,
+                         wbfm_stereo_receiver)
 
 version = "0.1.0"

@@ -744,6 +744,80 @@ class BinaryPhaseCorrectorBlock(Block):
         return self._execute(x, np.complex64)
 
 
+# ---- carrier recovery (luaradio_amd/csrc/stage_pll.h)
+def pll_coefficients(loop_bandwidth, frequency_min, frequency_max, rate):
+    """PLLBlock:initialize (pll.lua:117-126) in its operation order: (alpha, beta, freq_min, freq_max), frequencies in radians per sample."""
+    loop_bw = 2 * math.pi * (loop_bandwidth / rate)
+    freq_min = 2 * math.pi * (frequency_min / rate)
+    freq_max = 2 * math.pi * (frequency_max / rate)
+    damping = math.sqrt(2) / 2
+    loop_bw = loop_bw / (damping + 1 / (4 * damping))
+    denom = (1 + 2 * damping * loop_bw + loop_bw * loop_bw)
+    alpha = (4 * damping * loop_bw) / denom
+    beta = (4 * loop_bw * loop_bw) / denom
+    return alpha, beta, freq_min, freq_max
+
+
+class PLLOutBlock(Block):
+    """One output port of PLLBlock as a one-output block: "out" (ComplexFloat32, cis(phi_multiplied)) or "error" (Float32).  The receivers that
+    use the PLL's `out` alone take this block, so the loop runs once per call."""
+    name = "PLLBlock"
+    op_knobs = ""       # further "key=value" text for the op string (stage_pll.h: ":segment=64", ":warmup=8", ":speculate=0"), for tests and tools
+
+    def instantiate(self, loop_bandwidth=None, frequency_min=None, frequency_max=None, multiplier=1.0, port="out"):
+        assert loop_bandwidth is not None, "Missing argument #1 (loop_bandwidth)"
+        assert frequency_min is not None, "Missing argument #2 (frequency_min)"
+        assert frequency_max is not None, "Missing argument #3 (frequency_max)"
+        assert port in ("out", "error"), 'port should be "out" or "error"'
+        self.loop_bandwidth, self.frequency_min, self.frequency_max = loop_bandwidth, frequency_min, frequency_max
+        self.multiplier = 1.0 if multiplier is None else multiplier
+        self.port = port
+        self.add_type_signature([Input("in", types.ComplexFloat32)], [Output(port, types.ComplexFloat32 if port == "out" else types.Float32)])
+
+    def op(self):
+        alpha, beta, freq_min, freq_max = pll_coefficients(self.loop_bandwidth, self.frequency_min, self.frequency_max, self.get_rate())
+        return digital_op("pll", alpha=alpha, beta=beta, fmin=freq_min, fmax=freq_max, mult=self.multiplier) + ":port=" + self.port + self.op_knobs
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 1), "Creating lrhip pll object")
+
+    def process(self, x):
+        return self._execute(x, self.get_output_type().dtype)
+
+
+class PLLBlock(Block):
+    """radio/blocks/signal/pll.lua. PLLBlock(loop_bandwidth, frequency_min, frequency_max[, multiplier=1.0]): ComplexFloat32 -> out
+    (ComplexFloat32, the locked oscillator at `multiplier` times the input's phase) and error (Float32, the phase detector).  One stage per
+    port: the loop is deterministic, so both run the same trajectory from the same state.  Parallel in time while the loop is in lock
+    (luaradio_amd/csrc/pll_plan.h: the contract); process(x) returns (out, error)."""
+    name = "PLLBlock"
+    op_knobs = ""       # as PLLOutBlock.op_knobs, handed to both ports' stages
+
+    def instantiate(self, loop_bandwidth=None, frequency_min=None, frequency_max=None, multiplier=1.0):
+        assert loop_bandwidth is not None, "Missing argument #1 (loop_bandwidth)"
+        assert frequency_min is not None, "Missing argument #2 (frequency_min)"
+        assert frequency_max is not None, "Missing argument #3 (frequency_max)"
+        self.loop_bandwidth, self.frequency_min, self.frequency_max = loop_bandwidth, frequency_min, frequency_max
+        self.multiplier = 1.0 if multiplier is None else multiplier
+        self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32), Output("error", types.Float32)])
+
+    def initialize(self):
+        self._out, self._error = (PLLOutBlock(self.loop_bandwidth, self.frequency_min, self.frequency_max, self.multiplier, port) for port in ("out", "error"))
+        self._sub_blocks = [self._out, self._error]       # DeviceGraph: one device pass per output
+        for b in self._sub_blocks:
+            b.rate = self.get_rate()
+            b.op_knobs = self.op_knobs
+            b.differentiate([types.ComplexFloat32])
+            b.initialize()
+
+    def process(self, x):
+        return self._out.process(x), self._error.process(x)
+
+    def reset(self):
+        for b in self._sub_blocks:
+            b.reset()
+
+
 # ---- the ERT receiver's blocks (luaradio_amd/csrc/stage_preamble.h)
 PREAMBLE_SAMPLER_MAX_BUFFER = 1 << 21       # PS_MAX_B: the largest circular buffer 2^ceil_log2(period * #preamble + 1) the library accepts
 

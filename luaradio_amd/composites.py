@@ -454,6 +454,57 @@ def nbfm_receiver(rate=1102500.0, tune_offset=-100e3, deviation=5e3, bandwidth=4
                       B.LowpassFilterBlock(128, bandwidth)], rate)
 
 
+def am_synchronous_receiver(rate=1102500.0, ifreq=50e3, bandwidth=5e3):
+    """The compute blocks of examples/rtlsdr_am_synchronous.lua:14-22 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`):
+    Decimator(5) -> ComplexBandpass(129, {ifreq - bw, ifreq + bw}), mixed (MultiplyConjugate) with PLL(1000, ifreq - 100, ifreq + 100) locked to
+    it, -> ComplexToReal -> SinglepoleHighpass(100) -> Lowpass(128, bw) -> Downsampler(10) -> AGC('slow').  The PLL's `out` port alone is used,
+    so the loop runs once per call.  g.process(**{"in": x}) returns {"AGCBlock": audio}."""
+    from .graph import DeviceGraph
+    g = DeviceGraph()
+    src = g.input("in", types.ComplexFloat32, rate)
+    if_filter = B.ComplexBandpassFilterBlock(129, [ifreq - bandwidth, ifreq + bandwidth])
+    pll = B.PLLOutBlock(1000, ifreq - 100, ifreq + 100)
+    mixer = B.MultiplyConjugateBlock()
+    g.connect(src, DecimatorBlock(5), if_filter)
+    g.connect(if_filter, pll)
+    g.connect(if_filter, "out", mixer, "in1")
+    g.connect(pll, "out", mixer, "in2")
+    g.connect(mixer, B.ComplexToRealBlock(), B.SinglepoleHighpassFilterBlock(100), B.LowpassFilterBlock(128, bandwidth), B.DownsamplerBlock(10),
+              B.AGCBlock("slow"))
+    return g.initialize()
+
+
+def wbfm_stereo_receiver(rate=1102500.0, tune_offset=-250e3):
+    """The compute blocks of examples/rtlsdr_wbfm_stereo.lua:13-33 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`):
+    Tuner(offset, 200e3, 5) -> FrequencyDiscriminator(1.25) -> Hilbert(129), whose output feeds Delay(129) and the pilot branch
+    ComplexBandpass(129, {18e3, 20e3}) -> PLL(100, 18950, 19050, 2).  L+R = Lowpass(128, 15e3) -> ComplexToReal of the delayed signal, L-R the same
+    of MultiplyConjugate(delayed, pll); left = Add, right = Subtract, each -> FMDeemphasis(75e-6) -> Downsampler(5).
+    g.process(**{"in": x}) returns {"left": audio, "right": audio}."""
+    from .graph import DeviceGraph
+    g = DeviceGraph()
+    src = g.input("in", types.ComplexFloat32, rate)
+    hilbert, delay = B.HilbertTransformBlock(129), B.DelayBlock(129)
+    pilot_pll = B.PLLOutBlock(100, 19e3 - 50, 19e3 + 50, 2)
+    mixer = B.MultiplyConjugateBlock()
+    lpr_am_demod, lmr_am_demod = B.ComplexToRealBlock(), B.ComplexToRealBlock()
+    l_summer, r_subtractor = B.AddBlock(), B.SubtractBlock()
+    l_downsampler, r_downsampler = B.DownsamplerBlock(5), B.DownsamplerBlock(5)
+    l_downsampler.name, r_downsampler.name = "left", "right"      # the keys of the two outputs in process()'s result
+    g.connect(src, TunerBlock(tune_offset, 200e3, 5), B.FrequencyDiscriminatorBlock(1.25), hilbert, delay)
+    g.connect(hilbert, B.ComplexBandpassFilterBlock(129, [18e3, 20e3]), pilot_pll)
+    g.connect(delay, "out", mixer, "in1")
+    g.connect(pilot_pll, "out", mixer, "in2")
+    g.connect(delay, B.LowpassFilterBlock(128, 15e3), lpr_am_demod)
+    g.connect(mixer, B.LowpassFilterBlock(128, 15e3), lmr_am_demod)
+    g.connect(lpr_am_demod, "out", l_summer, "in1")
+    g.connect(lmr_am_demod, "out", l_summer, "in2")
+    g.connect(lpr_am_demod, "out", r_subtractor, "in1")
+    g.connect(lmr_am_demod, "out", r_subtractor, "in2")
+    g.connect(l_summer, B.FMDeemphasisFilterBlock(75e-6), l_downsampler)
+    g.connect(r_subtractor, B.FMDeemphasisFilterBlock(75e-6), r_downsampler)
+    return g.initialize()
+
+
 # ---- digital receivers up to the bit stream.  The framers and decoders behind them (AX25FramerBlock, POCSAGFramerBlock / POCSAGDecoderBlock,
 # VaricodeDecoderBlock) are bit-level state machines and stay in the reference (DESIGN.md §8).
 def ax25_receiver(rate=1e6, tune_offset=-100e3):

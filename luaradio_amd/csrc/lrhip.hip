@@ -29,6 +29,7 @@
 #include "kernels_preamble.h"
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
+#include "kernels_pll.h"
 
 using namespace lrhip;
 
@@ -54,6 +55,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "chain.h"
 #include "stage_phasecorr.h"
 #include "stage_digital.h"
+#include "stage_pll.h"
 #include "stage_preamble.h"
 #include "stage_modulator.h"
 #include "chain_plan.h"
@@ -403,6 +405,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "preamblesampler") return preamblesampler_create(op);
         // the modulators carry their symbol table as a list (stage_modulator.h)
         if (head == "pam" || head == "qam") return modulator_create(op);
+        // the PLL names its output port in words (stage_pll.h)
+        if (head == "pll") return pll_create(op);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

@@ -1,0 +1,128 @@
+// stage_pll.h - PLLBlock (kernels_pll.h, pll_plan.h), created through lrhip_unary_create("pll:alpha=..:beta=..:fmin=..:fmax=..:mult=..:port=out|error").
+// alpha, beta, fmin and fmax are in radians per sample, computed by the caller in double in the operation order of pll.lua:117-126; port =
+// out (ComplexFloat32 cis(phi_multiplied), the default) or error (Float32).  Test knobs: segment= (C), warmup= (W), speculate=0 (serial path only).
+// The stage fuses with nothing (chain_plan.h knows no rule for it) and cannot be sharded in time: no finite halo reproduces an unlocked loop.
+// A call launches 1 kernel on the serial path, 4 on the speculative one, 5 when the verify pass rejected a segment (Chain.last_launches).
+// (part of liblrhip.so; included by lrhip.hip before stage_digital.h, one translation unit)
+#pragma once
+
+struct PllStage : lrhip_stage {
+    PllParams p;
+    int port = PLL_PORT_OUT;
+    unsigned long W = 0, seg_req = 0;        // warm-up length (0: none, serial only); "segment=" (0: chosen per call)
+    bool allow = true;                       // "speculate=0" clears it
+    DeviceBuf state, scratch;                // state: PllState ping-pong, then PllStats
+    PinnedBuf h_rej;
+    int cur = 0;
+    const char *kind() const override { return port == PLL_PORT_OUT ? "pll" : "pll(error)"; }
+    long memory() const override { return -1; }
+    int reset() override
+    {
+        PllState s[3];
+        memset(s, 0, sizeof(s));                             // the third slot holds PllStats (two counters)
+        s[0] = s[1] = pll_initial(p);
+        cur = 0;
+        return upload(state, s, sizeof(s));
+    }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (n > cap) return set_error("%s: output capacity %lu < %lu", kind(), cap, n);
+        if (!n) return 0;
+        const PllPlan q = pll_make_plan(n, p, W, (unsigned long)ctx().num_cus * 512, seg_req, allow);
+        const PllState *si = (const PllState *)state.p + cur;
+        PllState *so = (PllState *)state.p + (cur ^ 1);
+        PllStats *stats = (PllStats *)((PllState *)state.p + 2);
+        const float *x = (const float *)in_dev;
+        if (!q.speculate) {
+            if (port == PLL_PORT_OUT) hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_OUT>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, si, out_dev, so, stats);
+            else hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_ERROR>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, si, out_dev, so, stats);
+            LR_LAUNCH_CHECK();
+            cur ^= 1;
+            return (long)n;
+        }
+        // scratch: entry and exit edges, phi_multiplied totals / entries, the segments' mean |err|, rejection flags
+        const size_t o_exit = q.nseg * sizeof(PllEdge), o_pm = o_exit + q.nseg * sizeof(PllEdge), o_emean = o_pm + q.nseg * sizeof(double),
+                     o_bad = o_emean + q.nseg * sizeof(double), total = o_bad + q.nseg;
+        if (scratch.reserve(total)) return -1;
+        char *sp = (char *)scratch.p;
+        PllEdge *entry = (PllEdge *)sp, *exit_ = (PllEdge *)(sp + o_exit);
+        double *pm = (double *)(sp + o_pm);
+        double *emean = (double *)(sp + o_emean);
+        unsigned char *bad = (unsigned char *)(sp + o_bad);
+        const unsigned lanes_grid = (unsigned)((q.nseg + 63) / 64);
+        hipLaunchKernelGGL(pll_speculate_kernel, dim3(lanes_grid), dim3(64), 0, ctx().stream, x, n, p, q.C, q.W, q.nseg, si, entry, exit_, pm, emean, stats);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pll_verify_kernel, dim3((unsigned)((q.nseg + 255) / 256)), dim3(256), 0, ctx().stream, (const PllEdge *)entry, (const PllEdge *)exit_, (const double *)emean, q.nseg,
+                           q.tol_phi, q.tol_f, bad, stats);
+        LR_LAUNCH_CHECK();
+        // did the loop hold lock?  The one small read-back of this stage: the repair walk is launched only when a segment was rejected
+        if (h_rej.reserve(sizeof(unsigned long long))) return -1;
+        LR_HIP(hipMemcpyAsync(h_rej.p, &stats->rejected, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
+        LR_HIP(hipStreamSynchronize(ctx().stream));
+        if (*(const unsigned long long *)h_rej.p) {
+            hipLaunchKernelGGL(pll_repair_kernel, dim3(1), dim3(64), 0, ctx().stream, x, n, p, q.C, q.nseg, q.tol_phi, q.tol_f, bad, entry, exit_, pm, (const double *)emean, stats);
+            LR_LAUNCH_CHECK();
+        }
+        hipLaunchKernelGGL(pll_prefix_kernel, dim3(1), dim3(256), 0, ctx().stream, pm, q.nseg, si);
+        LR_LAUNCH_CHECK();
+        if (port == PLL_PORT_OUT)
+            hipLaunchKernelGGL((pll_emit_kernel<PLL_PORT_OUT>), dim3(lanes_grid), dim3(64), 0, ctx().stream, x, n, p, q.C, q.nseg, (const PllEdge *)entry, (const double *)pm,
+                               out_dev, so);
+        else
+            hipLaunchKernelGGL((pll_emit_kernel<PLL_PORT_ERROR>), dim3(lanes_grid), dim3(64), 0, ctx().stream, x, n, p, q.C, q.nseg, (const PllEdge *)entry,
+                               (const double *)pm, out_dev, so);
+        LR_LAUNCH_CHECK();
+        cur ^= 1;
+        return (long)n;
+    }
+};
+
+static const std::initializer_list<const char *> pll_keys = {"alpha", "beta", "fmin", "fmax", "mult", "segment", "warmup", "speculate"};
+
+static lrhip_stage_t *pll_create(const char *op)
+{
+    // "port=out" / "port=error" is the one value that is no number: taken out of the string before parse_op reads the rest
+    std::string rest(op), name;
+    std::map<std::string, double> kv;
+    const size_t at = rest.find(":port=");
+    if (at != std::string::npos) {
+        const size_t end = rest.find(':', at + 1);
+        const std::string v = rest.substr(at + 6, end == std::string::npos ? std::string::npos : end - at - 6);
+        if (v != "out" && v != "error") { set_error("pll: port must be \"out\" or \"error\", not \"%s\"", v.c_str()); return nullptr; }
+        rest.erase(at, end == std::string::npos ? std::string::npos : end - at);
+        if (rest.find(":port=") != std::string::npos) { set_error("pll: parameter \"port\" given twice"); return nullptr; }
+        kv["port"] = v == "error" ? 1.0 : 0.0;
+    }
+    {
+        std::map<std::string, double> nums;
+        if (!parse_op(rest.c_str(), name, nums, pll_keys)) return nullptr;
+        kv.insert(nums.begin(), nums.end());
+    }
+    PllParams p;
+    struct { const char *k; double *v; } need[] = {{"alpha", &p.alpha}, {"beta", &p.beta}, {"fmin", &p.fmin}, {"fmax", &p.fmax}};
+    for (auto &f : need) {
+        auto it = kv.find(f.k);
+        if (it == kv.end()) { set_error("pll: missing parameter \"%s\" in \"%s\"", f.k, op); return nullptr; }
+        if (!std::isfinite(it->second)) { set_error("pll: %s must be finite", f.k); return nullptr; }
+        *f.v = it->second;
+    }
+    p.mult = kv.count("mult") ? kv.at("mult") : 1.0;         // pll.lua:32
+    if (!std::isfinite(p.mult)) { set_error("pll: mult must be finite"); return nullptr; }
+    const double port = kv.count("port") ? kv.at("port") : 0.0, seg = kv.count("segment") ? kv.at("segment") : 0.0,
+                 warm = kv.count("warmup") ? kv.at("warmup") : -1.0, spec = kv.count("speculate") ? kv.at("speculate") : 1.0;
+    if (spec != 0.0 && spec != 1.0) { set_error("pll: speculate must be 0 or 1"); return nullptr; }
+    if (kv.count("segment") && (!(seg >= 1.0 && seg <= 1073741824.0) || seg != floor(seg))) { set_error("pll: segment must be an integer in [1, 2^30]"); return nullptr; }
+    if (kv.count("warmup") && (!(warm >= 1.0 && warm <= 1073741824.0) || warm != floor(warm))) { set_error("pll: warmup must be an integer in [1, 2^30]"); return nullptr; }
+    if (ensure_init()) return nullptr;
+    std::unique_ptr<PllStage> q(new (std::nothrow) PllStage());
+    if (!q) { set_error("out of memory"); return nullptr; }
+    q->p = p;
+    q->port = port == 0.0 ? PLL_PORT_OUT : PLL_PORT_ERROR;
+    q->seg_req = (unsigned long)seg;
+    q->W = kv.count("warmup") ? (unsigned long)warm : pll_warmup(p.alpha, p.beta, PLL_TOL_PHI / 256.0);
+    q->allow = spec != 0.0;
+    q->in_size = 8;
+    q->out_size = q->port == PLL_PORT_OUT ? 8 : 4;
+    if (q->reset()) return nullptr;
+    return q.release();
+}
