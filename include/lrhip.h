@@ -165,6 +165,14 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *   "manchesterdecoder:invert=0|1"                     (manchesterdecoder.lua:31-61) Bit -> Bit (input bytes read as & 1): a 0,1 pair gives 0 ^ invert, a
  *                                                      1,0 pair 1 ^ invert, an equal pair is a clock slip and the newer bit stays pending; count
  *                                                      data-dependent (<= (n + 1) / 2).
+ *   "rdsframer"                                        (rdsframer.lua:95-201; no parameters, any is refused) Bit -> 8-byte records
+ *                                                      {uint16_t blocks[4]}, little-endian: the data words A, B, C, D of every 104-bit window whose four
+ *                                                      26-bit blocks have a zero or single-bit-error syndrome under the offset words A, B, C (C' only
+ *                                                      when C is uncorrectable) and D, single-bit errors corrected.  A byte counts as 1 only when it
+ *                                                      equals 1.  Windows are tested from the first bit no accepted frame has consumed; an accepted
+ *                                                      frame moves that bit 104 on, so a valid window inside an accepted frame is not emitted.  Count
+ *                                                      data-dependent (<= (n + 103) / 104); the carried state is the at most 103 bits since that bit;
+ *                                                      bit-identical however the stream is cut.  Fuses with nothing.
  *   "pam:period=P:bits=b:msb=0|1:table=a0,a1,..."     (pulseamplitudemodulator.lua:57-87) Bit -> Float32: b bits (a byte counts as 1 only when it equals
  *                                                      1; msb=1: the first bit is the most significant) select one of the 2^b table entries, which is
  *                                                      held for P output samples.  P = floor(sample_rate / symbol_rate) in 1 .. 2^30 - 1, b in 1 .. 16,
@@ -174,7 +182,8 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
- * The sampler, the clocksampler, the preamblesampler and the manchesterdecoder have memory() -1: chains holding them refuse time partitions. */
+ * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder and the rdsframer have memory() -1: chains holding them refuse time
+ * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */
 lrhip_stage_t *lrhip_delay_create(unsigned num_samples, int elem_size);

@@ -6,6 +6,7 @@ C ABI of liblrhip.so (include/lrhip.h).  The Lua glue a LuaRadio checkout would 
 from . import _lib, filter_utils, spectrum_utils, types, window_utils  # noqa: F401
 from ._lib import LrhipError, adopt_torch_stream, init  # noqa: F401
 from .block import Block, Input, Output  # noqa: F401
+from .types import RDSFrameType  # noqa: F401
 from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock, FIRFilterBlock,  # noqa: F401
                      FMDeemphasisFilterBlock, FrequencyDiscriminatorBlock, FrequencyTranslatorBlock,
                      HighpassFilterBlock, IIRFilterBlock, LowpassFilterBlock, SinglepoleLowpassFilterBlock,
@@ -16,7 +17,7 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      FMPreemphasisFilterBlock, FloatToComplexBlock, ComplexToFloatBlock, FrequencyModulatorBlock,
                      PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
                      ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock,
-                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock,
+                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock, RDSFramerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401
@@ -25,6 +26,6 @@ from .graph import DeviceGraph  # noqa: F401
 from .composites import (Chain, CompositeBlock, DecimatorBlock, InterpolatorBlock, RationalResamplerBlock, TunerBlock, WBFMMonoDemodulator,  # noqa: F401
                          NBFMDemodulator, AMEnvelopeDemodulator, SSBDemodulator, SSBModulator, wbfm_mono_receiver, am_envelope_receiver,
                          ssb_receiver, nbfm_receiver, ax25_receiver, pocsag_receiver, bpsk31_receiver, ert_receiver, am_synchronous_receiver,
-                         wbfm_stereo_receiver)
+                         wbfm_stereo_receiver, rds_receiver)
 
 version = "0.1.0"

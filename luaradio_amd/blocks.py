@@ -896,6 +896,25 @@ class ManchesterDecoderBlock(Block):
         return self._execute(x, np.uint8)
 
 
+class RDSFramerBlock(Block):
+    """radio/blocks/protocol/rdsframer.lua. RDSFramerBlock(): Bit -> RDSFrameType, one record of four 16-bit data words per 104-bit window whose
+    four blocks check (single-bit errors corrected); after a frame the search resumes behind it.  The output count depends on the data;
+    process(x) returns an (n, 4) uint16 array."""
+    name = "RDSFramerBlock"
+
+    def instantiate(self):
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.RDSFrameType)])
+
+    def op(self):
+        return "rdsframer"
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip rdsframer object")
+
+    def process(self, x):
+        return self._execute(x, types.RDSFrameType.dtype)
+
+
 # ---- the Bit -> sample blocks (luaradio_amd/csrc/stage_modulator.h)
 MODULATOR_MAX_BITS = 16                     # MOD_MAX_BITS: the symbol table holds at most 2^16 entries
 

@@ -505,8 +505,37 @@ def wbfm_stereo_receiver(rate=1102500.0, tune_offset=-250e3):
     return g.initialize()
 
 
+def rds_receiver(rate=1102500.0, tune_offset=-250e3, framer=True):
+    """The compute blocks of examples/rtlsdr_rds.lua:13-30 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`):
+    Tuner(offset, 200e3, 5) -> FrequencyDiscriminator(1.25) -> Hilbert(129), whose output feeds Delay(129) and the pilot branch
+    ComplexBandpass(129, {18e3, 20e3}) -> PLL(1500, 18900, 19100, 3): the 57 kHz subcarrier.  MultiplyConjugate(delayed, pll) -> Lowpass(128, 4e3)
+    -> RootRaisedCosine(101, 1, 1187.5) -> BinaryPhaseCorrector(8000) -> ComplexToReal -> ClockSampler(2375) -> Slicer -> ManchesterDecoder ->
+    DifferentialDecoder -> RDSFramer.  The reference samples the complex corrected signal at the clock recovered from its real part and then
+    takes the real part (:49-52): the same as sampling the real part (bpsk31_receiver), so the tail is linear.  The PLL's `out` port alone is
+    used, so the loop runs once per call.  g.process(**{"in": x}) returns {"frames": (n, 4) uint16}; with framer=False the graph ends at the
+    differential decoder and returns {"bits": uint8}, the stream the reference's RDSFramerBlock reads.  RDSDecoderBlock (frames -> packets)
+    stays in the reference."""
+    from .graph import DeviceGraph
+    g = DeviceGraph()
+    src = g.input("in", types.ComplexFloat32, rate)
+    hilbert, delay = B.HilbertTransformBlock(129), B.DelayBlock(129)
+    pll = B.PLLOutBlock(1500.0, 19e3 - 100, 19e3 + 100, 3.0)
+    mixer = B.MultiplyConjugateBlock()
+    tail = [B.LowpassFilterBlock(128, 4e3), B.RootRaisedCosineFilterBlock(101, 1, 1187.5), B.BinaryPhaseCorrectorBlock(8000), B.ComplexToRealBlock(),
+            B.ClockSamplerBlock(1187.5 * 2), B.SlicerBlock(), B.ManchesterDecoderBlock(), B.DifferentialDecoderBlock()]
+    if framer:
+        tail.append(B.RDSFramerBlock())
+    tail[-1].name = "frames" if framer else "bits"           # the key of the output in process()'s result
+    g.connect(src, TunerBlock(tune_offset, 200e3, 5), B.FrequencyDiscriminatorBlock(1.25), hilbert, delay)
+    g.connect(hilbert, B.ComplexBandpassFilterBlock(129, [18e3, 20e3]), pll)
+    g.connect(delay, "out", mixer, "in1")
+    g.connect(pll, "out", mixer, "in2")
+    g.connect(mixer, *tail)
+    return g.initialize()
+
+
 # ---- digital receivers up to the bit stream.  The framers and decoders behind them (AX25FramerBlock, POCSAGFramerBlock / POCSAGDecoderBlock,
-# VaricodeDecoderBlock) are bit-level state machines and stay in the reference.
+# VaricodeDecoderBlock) stay in the reference (DESIGN.md §8); of the framers only RDSFramerBlock has a device form (rds_receiver).
 def ax25_receiver(rate=1e6, tune_offset=-100e3):
     """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, up to the Bit stream AX25FramerBlock reads:
     Tuner(offset, 12e3, 80) -> NBFMDemodulator(3e3, 3e3) -> Hilbert(129) -> Translator(-1700) -> Lowpass(128, 750) -> Discriminator(1.25)

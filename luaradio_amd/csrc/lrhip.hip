@@ -27,6 +27,7 @@
 #include "kernels_rx.h"
 #include "kernels_digital.h"
 #include "kernels_preamble.h"
+#include "kernels_rdsframer.h"
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
 #include "kernels_pll.h"
@@ -57,6 +58,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_digital.h"
 #include "stage_pll.h"
 #include "stage_preamble.h"
+#include "stage_rdsframer.h"
 #include "stage_modulator.h"
 #include "chain_plan.h"
 
@@ -407,6 +409,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "pam" || head == "qam") return modulator_create(op);
         // the PLL names its output port in words (stage_pll.h)
         if (head == "pll") return pll_create(op);
+        // the RDS framer takes no parameters at all (stage_rdsframer.h)
+        if (head == "rdsframer") return rdsframer_create(op);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);
