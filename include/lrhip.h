@@ -173,6 +173,32 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      frame moves that bit 104 on, so a valid window inside an accepted frame is not emitted.  Count
  *                                                      data-dependent (<= (n + 103) / 104); the carried state is the at most 103 bits since that bit;
  *                                                      bit-identical however the stream is cut.  Fuses with nothing.
+ *   "scmframer" | "scmplusframer" | "idmframer"        (scmframer.lua:166-211, scmplusframer.lua:181-225, idmframer.lua:187-243; no parameters, any is
+ *                                                      refused) Bit -> one little-endian record per frame, pad bytes zero, numeric fields the
+ *                                                      reference's Bit.tonumber values:
+ *                                                        struct lrhip_scm_frame {       16 bytes, per 96-bit window
+ *                                                          uint32_t ert_id, consumption; uint16_t crc;
+ *                                                          uint8_t ert_type, physical_tamper, encoder_tamper, reserved, pad[2]; };
+ *                                                        struct lrhip_scmplus_frame {   16 bytes, per 128-bit window
+ *                                                          uint32_t ert_id, consumption; uint16_t tamper, crc;
+ *                                                          uint8_t protocol_id, ert_type, pad[2]; };
+ *                                                        struct lrhip_idm_frame {       88 bytes, per 736-bit window
+ *                                                          uint32_t ert_id, last_consumption_count;
+ *                                                          uint16_t transmit_time_offset, serial_crc, packet_crc;
+ *                                                          uint8_t application_version, ert_type, consumption_interval_count, module_programming_state;
+ *                                                          uint8_t tamper_count[6], async_count[2], power_outage_flags[6],
+ *                                                                  differential_consumption_intervals[53], pad[3]; };
+ *                                                      (the byte arrays as Bit.tobytes packs them: MSB first, in frame order).  A window is a frame
+ *                                                      when it starts with the preamble / sync word (21 bits 0x1f2a60, 16 bits 0x16a3, 32 bits
+ *                                                      0x555516a3), the codeword behind it (75, 112, 704 bits) has a zero or single-bit-error syndrome
+ *                                                      (the erroneous byte b replaced by (~b) & 1), and then protocol_id == 0x1e (SCM+) or packet type
+ *                                                      0x1c, length 0x5cc6 and serial CRC (IDM) hold.  A byte counts as 1 only when it equals 1; the
+ *                                                      IDM serial CRC alone reads byte values as idm_compute_crc does.  As in the reference the
+ *                                                      correction is made in the buffer: an SCM+ / IDM window that corrects a byte and then fails its
+ *                                                      later check is rejected with the corrected byte left for the windows after it.  An accepted
+ *                                                      frame moves the search L bits on.  Count data-dependent (<= (n + L - 1) / L); the carried
+ *                                                      state is the at most L - 1 bytes (corrections applied) since the first bit no accepted frame
+ *                                                      has consumed; bit-identical however the stream is cut.  Fuses with nothing.
  *   "pam:period=P:bits=b:msb=0|1:table=a0,a1,..."     (pulseamplitudemodulator.lua:57-87) Bit -> Float32: b bits (a byte counts as 1 only when it equals
  *                                                      1; msb=1: the first bit is the most significant) select one of the 2^b table entries, which is
  *                                                      held for P output samples.  P = floor(sample_rate / symbol_rate) in 1 .. 2^30 - 1, b in 1 .. 16,
@@ -182,7 +208,7 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
- * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder and the rdsframer have memory() -1: chains holding them refuse time
+ * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the rdsframer and the three ERT framers have memory() -1: chains holding them refuse time
  * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */

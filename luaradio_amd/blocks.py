@@ -915,6 +915,48 @@ class RDSFramerBlock(Block):
         return self._execute(x, types.RDSFrameType.dtype)
 
 
+class _ERTFramerBlock(Block):
+    """The three ERT framers (luaradio_amd/csrc/stage_ertframer.h): Bit -> one structured record per frame.  They follow the reference's
+    process() loops literally, the single-bit correction made inside the shift buffer included: a window that corrects a bit and then fails a
+    later check leaves the flip behind for the windows after it.  The output count depends on the data; process(x) returns a structured array
+    of the block's frame type, whose fields carry the reference's names."""
+    _op = _frame_type = None
+
+    def instantiate(self):
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", self._frame_type)])
+
+    def op(self):
+        return self._op
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self._op)
+
+    def process(self, x):
+        return self._execute(x, self._frame_type.dtype)
+
+
+class SCMFramerBlock(_ERTFramerBlock):
+    """radio/blocks/protocol/scmframer.lua. SCMFramerBlock(): Bit -> SCMFrameType, one 16-byte record per 96-bit window that starts with the
+    21-bit preamble 0x1f2a60 and whose 75-bit codeword is correctable (BCH, single-bit errors corrected)."""
+    name = "SCMFramerBlock"
+    _op, _frame_type = "scmframer", types.SCMFrameType
+
+
+class SCMPlusFramerBlock(_ERTFramerBlock):
+    """radio/blocks/protocol/scmplusframer.lua. SCMPlusFramerBlock(): Bit -> SCMPlusFrameType, one 16-byte record per 128-bit window that
+    starts with the sync word 0x16a3, whose 112-bit codeword is correctable and whose protocol id is 0x1e."""
+    name = "SCMPlusFramerBlock"
+    _op, _frame_type = "scmplusframer", types.SCMPlusFrameType
+
+
+class IDMFramerBlock(_ERTFramerBlock):
+    """radio/blocks/protocol/idmframer.lua. IDMFramerBlock(): Bit -> IDMFrameType, one 88-byte record per 736-bit window that starts with the
+    preamble 0x5555 and the sync word 0x16a3, whose 704-bit codeword is correctable, whose packet type and length are 0x1c and 0x5cc6 and whose
+    serial CRC matches."""
+    name = "IDMFramerBlock"
+    _op, _frame_type = "idmframer", types.IDMFrameType
+
+
 # ---- the Bit -> sample blocks (luaradio_amd/csrc/stage_modulator.h)
 MODULATOR_MAX_BITS = 16                     # MOD_MAX_BITS: the symbol table holds at most 2^16 entries
 

@@ -535,7 +535,8 @@ def rds_receiver(rate=1102500.0, tune_offset=-250e3, framer=True):
 
 
 # ---- digital receivers up to the bit stream.  The framers and decoders behind them (AX25FramerBlock, POCSAGFramerBlock / POCSAGDecoderBlock,
-# VaricodeDecoderBlock) stay in the reference; of the framers only RDSFramerBlock has a device form (rds_receiver).
+# VaricodeDecoderBlock) stay in the reference; the framers with a device form are RDSFramerBlock (rds_receiver) and the three ERT
+# framers SCMFramerBlock, SCMPlusFramerBlock and IDMFramerBlock (ert_receiver with framers=True).
 def ax25_receiver(rate=1e6, tune_offset=-100e3):
     """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, up to the Bit stream AX25FramerBlock reads:
     Tuner(offset, 12e3, 80) -> NBFMDemodulator(3e3, 3e3) -> Hilbert(129) -> Translator(-1700) -> Lowpass(128, 750) -> Discriminator(1.25)
@@ -588,14 +589,17 @@ SCM_FRAME_LEN = 96                                                              
 SCM_PLUS_PREAMBLE = (0, 0, 0, 1, 0, 1, 1, 0, 1, 0, 1, 0, 0, 0, 1, 1)                                               # radio/blocks/protocol/scmplusframer.lua:45
 SCM_PLUS_FRAME_LEN = 128                                                                                         # scmplusframer.lua:46
 ERT_PROTOCOLS = {"idm": (IDM_PREAMBLE, IDM_FRAME_LEN), "scm": (SCM_PREAMBLE, SCM_FRAME_LEN), "scm+": (SCM_PLUS_PREAMBLE, SCM_PLUS_FRAME_LEN)}
+ERT_FRAMERS = {"idm": B.IDMFramerBlock, "scm": B.SCMFramerBlock, "scm+": B.SCMPlusFramerBlock}                    # ertreceiver.lua:44-69
 
 
-def ert_receiver(protocols=("idm", "scm", "scm+"), rate=None, decimation=6):
-    """The compute blocks of radio/composites/ertreceiver.lua:30-76 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`), up to the
-    Bit streams the IDM / SCM / SCM+ framers read: ComplexMagnitude -> Lowpass(128, 4 * 32768) -> Downsampler(decimation) ->
-    ManchesterMatchedFilter(32768), then per protocol PreambleSampler(16384, preamble, frame length) -> Slicer.
-    g.process(**{"in": x}) returns {protocol: bits}: each branch's slicer carries its protocol's name, so the three outputs do not meet on
-    one key."""
+def ert_receiver(protocols=("idm", "scm", "scm+"), rate=None, decimation=6, framers=False):
+    """The compute blocks of radio/composites/ertreceiver.lua:30-76 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`):
+    ComplexMagnitude -> Lowpass(128, 4 * 32768) -> Downsampler(decimation) -> ManchesterMatchedFilter(32768), then per protocol
+    PreambleSampler(16384, preamble, frame length) -> Slicer -> IDMFramer / SCMFramer / SCMPlusFramer.  By default the graph ends at the Bit
+    streams the framers read and g.process(**{"in": x}) returns {protocol: bits}; with framers=True each branch ends in its framer and the
+    result is {protocol: frames}, structured arrays of types.IDMFrameType / SCMFrameType / SCMPlusFrameType.  The last block of each branch
+    carries its protocol's name, so the three outputs do not meet on one key.  (The SCM+ branch also samples bits 16 .. 143 of every IDM
+    frame, whose preamble ends in the SCM+ sync word; its framer rejects them by the protocol id, as the reference's does.)"""
     from .graph import DeviceGraph
     assert rate is not None, "Missing argument #2 (rate)"
     symbol_rate = 32768
@@ -611,7 +615,9 @@ def ert_receiver(protocols=("idm", "scm", "scm+"), rate=None, decimation=6):
     g.connect(src, B.ComplexMagnitudeBlock(), B.LowpassFilterBlock(128, symbol_rate * 4), B.DownsamplerBlock(decimation), matched_filter)
     for protocol in protocols:
         preamble, frame_len = ERT_PROTOCOLS[protocol]
-        slicer = B.SlicerBlock()
-        slicer.name = protocol                     # the key of this branch in process()'s result
-        g.connect(matched_filter, B.PreambleSamplerBlock(symbol_rate / 2, preamble, frame_len), slicer)
+        tail = [B.SlicerBlock()]
+        if framers:
+            tail.append(ERT_FRAMERS[protocol]())
+        tail[-1].name = protocol                   # the key of this branch in process()'s result
+        g.connect(matched_filter, B.PreambleSamplerBlock(symbol_rate / 2, preamble, frame_len), *tail)
     return g.initialize()

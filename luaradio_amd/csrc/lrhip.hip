@@ -28,6 +28,7 @@
 #include "kernels_digital.h"
 #include "kernels_preamble.h"
 #include "kernels_rdsframer.h"
+#include "kernels_ertframer.h"
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
 #include "kernels_pll.h"
@@ -59,6 +60,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_pll.h"
 #include "stage_preamble.h"
 #include "stage_rdsframer.h"
+#include "stage_ertframer.h"
 #include "stage_modulator.h"
 #include "chain_plan.h"
 
@@ -411,6 +413,10 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "pll") return pll_create(op);
         // the RDS framer takes no parameters at all (stage_rdsframer.h)
         if (head == "rdsframer") return rdsframer_create(op);
+        // nor do the three ERT framers (stage_ertframer.h)
+        if (head == "scmframer") return ertframer_create<EF_SCM>(op);
+        if (head == "scmplusframer") return ertframer_create<EF_SCMPLUS>(op);
+        if (head == "idmframer") return ertframer_create<EF_IDM>(op);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

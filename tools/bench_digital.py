@@ -3,7 +3,8 @@
 decoder chain and the clock recovery alone, on resident Float32 samples; the binary phase corrector (kernels_phasecorr.h) alone on resident
 ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the three digital receivers up to their bit streams.  HIP-event timing on the launch stream after warm-up, as
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
-(4 B/sample read; + 4 B/sample written for the clock recovery)."""
+(4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators and --ert-framers print the rows of the PAM / QAM modulators and
+of the SCM / SCM+ / IDM framers instead (modulator_rows, ert_framer_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -20,10 +21,13 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--modulators", action="store_true", help="only the PAM / QAM modulator rows (profiles/modulator_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators: append the rows to this file as well")
+    ap.add_argument("--ert-framers", action="store_true", help="only the SCM / SCM+ / IDM framer rows (profiles/ert_framer_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --ert-framers: append the rows to this file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
+    if args.ert_framers:
+        return ert_framer_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -163,6 +167,66 @@ def modulator_rows(args):
     cap = chain.max_output(bits)
     ms = [timed(lambda: chain.process_device(x.data_ptr(), bits, y.data_ptr(), cap)) for _ in range(3)]
     emit({"row": "QAM(4) P=8 -> RRC(129)", "outputs": m_out, "ms": ms, "launches": chain.last_launches, "GS/s": round(m_out / min(ms) / 1e6, 2)})
+
+
+def ert_framer_rows(args):
+    """The three ERT framers (kernels_ertframer.h) on 2^log2-samples resident Bit bytes - random bits with a valid frame (the encoders of
+    tests/helpers/ert_framer_model.py) planted every 4 L bits - each next to a read-only pass over the same bytes (torch's sum: a yardstick for
+    the load stream, not one of the library's kernels), the two alternating three times.  A call includes the framer's one count read-back.
+    A record, not an acceptance criterion.  --out appends the rows to a file (profiles/ert_framer_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+    from tests.helpers import ert_framer_model as M
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+    n = 1 << args.log2_samples
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    for name, cls in (("scm", lr.SCMFramerBlock), ("scm+", lr.SCMPlusFramerBlock), ("idm", lr.IDMFramerBlock)):
+        P = M.PROTOCOLS[name]
+        bits = rng.integers(0, 2, n).astype(np.uint8)
+        frames = [M.random_frame(P, rng)[0] for _ in range(16)]
+        planted = 0
+        for at in range(P.L, n - P.L, 4 * P.L):
+            bits[at:at + P.L] = frames[planted % len(frames)]
+            planted += 1
+        x = torch.from_numpy(bits).cuda()
+        blk = cls()
+        blk.rate = 16384.0
+        blk.differentiate([types.Bit])
+        blk.initialize()
+        cap = blk.max_output(n)
+        y = torch.empty(cap * P.dtype.itemsize + 64, dtype=torch.uint8, device="cuda")
+        count = []
+
+        def call():                                   # successive calls continue one stream (the carried bytes of the call before)
+            count.append(blk.process_device(x.data_ptr(), n, y.data_ptr(), cap))
+        ms, ms_read = [], []
+        for _ in range(3):
+            ms.append(timed(call))
+            ms_read.append(timed(lambda: x.sum()))
+        row = {"row": "%s L=%d" % (cls.name, P.L), "bits": n, "frames_planted": planted, "frames_found": int(count[-1]), "ms": ms,
+               "read_only_ms": ms_read, "share_of_read_only": round(min(ms_read) / min(ms), 3), "Gbit/s": round(n / min(ms) / 1e6, 2)}
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":
