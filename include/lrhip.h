@@ -199,6 +199,54 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      frame moves the search L bits on.  Count data-dependent (<= (n + L - 1) / L); the carried
  *                                                      state is the at most L - 1 bytes (corrections applied) since the first bit no accepted frame
  *                                                      has consumed; bit-identical however the stream is cut.  Fuses with nothing.
+ *   "ax25framer"                                       (ax25framer.lua:94-284; no parameters, any is refused) Bit -> one little-endian record per frame,
+ *                                                      pad bytes and the tail of `data` behind `length` zero:
+ *                                                        struct lrhip_ax25_frame {      416 bytes
+ *                                                          uint16_t length;             octets in data: the unstuffed frame without its FCS, 13 .. 396
+ *                                                          uint16_t crc;                the received FCS, Bit.tonumber(frame, len - 16, 16, "lsb")
+ *                                                          uint8_t num_addresses;       addresses ax25_extract_frame walked (7 octets each, from data[0])
+ *                                                          uint8_t control, pid;        pid 0 when absent
+ *                                                          uint8_t has_pid;             0 when the reference's pid and payload are nil, else 1 (the
+ *                                                                                       payload may then be "")
+ *                                                          uint16_t payload_offset, payload_length;     the payload inside data
+ *                                                          uint8_t pad[4], data[400]; };                each octet Bit.tonumber(.., 8, "lsb")
+ *                                                      The consumed flags are the chain "first 8 bytes that read 0x7e at or after q, then q = p + 8";
+ *                                                      the bytes between two consecutive consumed flags are a frame when the segment before them was
+ *                                                      not emitted (the reference is IDLE behind a frame: one that shares its opening flag with an
+ *                                                      emitted frame's closing flag is lost), they are at most 3185, and unstuffed they are whole
+ *                                                      octets, at least 120 bits, the FCS matches and the address chain, the control octet and the
+ *                                                      optional PID / payload extract.  Bytes are read as the reference reads them: a byte is a 1 for
+ *                                                      the flag and the octets only when it equals 1; a byte is unstuffed only when it equals 0 behind
+ *                                                      exactly five bytes equal to 1; the CRC feeds back only when (crc & 1) ^ value == 1.  Count
+ *                                                      data-dependent (<= (n + 135) / 136: an emitted frame owns two flags and 120 bits); the carried
+ *                                                      state is the raw bytes of the open frame (at most 3185 + 7) or the last 7 bytes; bit-identical
+ *                                                      however the stream is cut.  Fuses with nothing.
+ *   "pocsagframer"                                     (pocsagframer.lua:120-277; no parameters, any is refused) Bit -> little-endian records, the tail
+ *                                                      of `data` behind `count` zero:
+ *                                                        struct lrhip_pocsag_frame {    256 bytes: one dword per lane of a wave
+ *                                                          uint32_t address;            21 bits
+ *                                                          uint8_t func;                2 bits
+ *                                                          uint8_t flags;               bit 0: this frame continues in the next record;
+ *                                                                                       bit 1: this record continues the previous one
+ *                                                          uint16_t count;              data words in this record, 0 .. 62
+ *                                                          uint32_t data[62]; };        20-bit data words
+ *                                                      The reference's frame has no upper length: a frame of more than 62 data words is a chain of
+ *                                                      records, a full one written with bit 0 set when the 63rd word arrives, its successor with bit 1
+ *                                                      and the same address and func.  Nothing is dropped.  FRAME_SYNC: the first position whose 32
+ *                                                      bytes correlate with the sync word, sum(s_i (2 value_i - 1)) >= 28 on the byte values.  BATCH,
+ *                                                      once 544 bytes are there: codeword 0 (a byte is a 1 only when it equals 1) must correct - zero or
+ *                                                      single-bit-error syndrome - to 0x7cd215d8, else the pending frame goes out, 32 bytes are
+ *                                                      consumed and the search resumes; then 16 codewords: uncorrectable, idle and address codewords
+ *                                                      emit the pending frame, an address codeword opens one, a data codeword appends to an open one,
+ *                                                      two uncorrectable in a row at position j consume (j + 1) 32 bytes and resume the search.
+ *                                                      TIMING: the reference takes one step per loop iteration after refilling its buffer, so it stops
+ *                                                      with up to 543 buffered bits unexamined and its output depends on how the stream was cut.  The
+ *                                                      stage is EAGER: it takes every step the bits seen so far allow (32 or more in FRAME_SYNC, 544 in
+ *                                                      BATCH).  Its output is the same however the stream is cut; whatever the reference emits for any
+ *                                                      cutting is a prefix of it; and it is a prefix of the reference's output once 544 further bits
+ *                                                      have been fed.  Count data-dependent (<= (n + 543) / 32: a record goes with 32 consumed
+ *                                                      bytes); the carried state is the pending frame and the at most 543 unconsumed bytes; reset
+ *                                                      drops both.  Fuses with nothing.
  *   "pam:period=P:bits=b:msb=0|1:table=a0,a1,..."     (pulseamplitudemodulator.lua:57-87) Bit -> Float32: b bits (a byte counts as 1 only when it equals
  *                                                      1; msb=1: the first bit is the most significant) select one of the 2^b table entries, which is
  *                                                      held for P output samples.  P = floor(sample_rate / symbol_rate) in 1 .. 2^30 - 1, b in 1 .. 16,
@@ -208,7 +256,7 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
- * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the rdsframer and the three ERT framers have memory() -1: chains holding them refuse time
+ * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time
  * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */

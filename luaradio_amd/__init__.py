@@ -6,7 +6,7 @@ C ABI of liblrhip.so (include/lrhip.h).  The Lua glue a LuaRadio checkout would 
 from . import _lib, filter_utils, spectrum_utils, types, window_utils  # noqa: F401
 from ._lib import LrhipError, adopt_torch_stream, init  # noqa: F401
 from .block import Block, Input, Output  # noqa: F401
-from .types import RDSFrameType, SCMFrameType, SCMPlusFrameType, IDMFrameType  # noqa: F401
+from .types import RDSFrameType, SCMFrameType, SCMPlusFrameType, IDMFrameType, AX25FrameType, POCSAGFrameType  # noqa: F401
 from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock, FIRFilterBlock,  # noqa: F401
                      FMDeemphasisFilterBlock, FrequencyDiscriminatorBlock, FrequencyTranslatorBlock,
                      HighpassFilterBlock, IIRFilterBlock, LowpassFilterBlock, SinglepoleLowpassFilterBlock,
@@ -18,7 +18,7 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
                      ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock,
                      BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock, RDSFramerBlock,
-                     SCMFramerBlock, SCMPlusFramerBlock, IDMFramerBlock,
+                     SCMFramerBlock, SCMPlusFramerBlock, IDMFramerBlock, AX25FramerBlock, POCSAGFramerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401

@@ -534,26 +534,31 @@ def rds_receiver(rate=1102500.0, tune_offset=-250e3, framer=True):
     return g.initialize()
 
 
-# ---- digital receivers up to the bit stream.  The framers and decoders behind them (AX25FramerBlock, POCSAGFramerBlock / POCSAGDecoderBlock,
-# VaricodeDecoderBlock) stay in the reference; the framers with a device form are RDSFramerBlock (rds_receiver) and the three ERT
-# framers SCMFramerBlock, SCMPlusFramerBlock and IDMFramerBlock (ert_receiver with framers=True).
-def ax25_receiver(rate=1e6, tune_offset=-100e3):
-    """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, up to the Bit stream AX25FramerBlock reads:
+# ---- digital receivers.  By default they end at the bit stream; every Bit -> frame framer of the reference has a device form: RDSFramerBlock
+# (rds_receiver), SCMFramerBlock, SCMPlusFramerBlock and IDMFramerBlock (ert_receiver with framers=True), AX25FramerBlock and POCSAGFramerBlock
+# (ax25_receiver and pocsag_receiver with framer=True).  The decoders behind them (POCSAGDecoderBlock, RDSDecoderBlock, VaricodeDecoderBlock)
+# stay in the reference.
+def ax25_receiver(rate=1e6, tune_offset=-100e3, framer=False):
+    """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, by default up to the Bit stream AX25FramerBlock reads:
     Tuner(offset, 12e3, 80) -> NBFMDemodulator(3e3, 3e3) -> Hilbert(129) -> Translator(-1700) -> Lowpass(128, 750) -> Discriminator(1.25)
     -> Lowpass(128, 1200) -> ClockSampler(1200) -> Slicer -> DifferentialDecoder(true).  ClockSampler(1200) is the reference's
     ZeroCrossingClockRecovery(1200) feeding the clock of a Sampler whose data is the same filtered signal (:34-36); the slicer and the
-    decoder run in its final pass."""
+    decoder run in its final pass.  With framer=True the chain ends in AX25FramerBlock and returns types.AX25FrameType records."""
     baudrate = 1200
-    return _receiver([TunerBlock(tune_offset, 12e3, 80), NBFMDemodulator(3e3, 3e3), B.HilbertTransformBlock(129), B.FrequencyTranslatorBlock(-1700),
-                      B.LowpassFilterBlock(128, 750), B.FrequencyDiscriminatorBlock(1.25), B.LowpassFilterBlock(128, baudrate),
-                      B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)], rate)
+    blocks = [TunerBlock(tune_offset, 12e3, 80), NBFMDemodulator(3e3, 3e3), B.HilbertTransformBlock(129), B.FrequencyTranslatorBlock(-1700),
+              B.LowpassFilterBlock(128, 750), B.FrequencyDiscriminatorBlock(1.25), B.LowpassFilterBlock(128, baudrate),
+              B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)]
+    if framer:
+        blocks.append(B.AX25FramerBlock())
+    return _receiver(blocks, rate)
 
 
-def pocsag_receiver(rate=1e6, tune_offset=-100e3, baudrate=1200):
-    """The compute blocks of examples/rtlsdr_pocsag.lua:14-23,33-41 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`), up to the
-    Bit stream POCSAGFramerBlock reads: Tuner(offset, 12e3, 80), then the space branch ComplexBandpass(129, {3500, 5500}) -> ComplexMagnitude and
+def pocsag_receiver(rate=1e6, tune_offset=-100e3, baudrate=1200, framer=False):
+    """The compute blocks of examples/rtlsdr_pocsag.lua:14-23,33-41 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`), by default up
+    to the Bit stream POCSAGFramerBlock reads: Tuner(offset, 12e3, 80), then the space branch ComplexBandpass(129, {3500, 5500}) -> ComplexMagnitude and
     the mark branch ComplexBandpass(129, {-5500, -3500}) -> ComplexMagnitude, joined by Subtract(mark, space) -> Lowpass(128, baudrate) ->
-    ClockSampler(baudrate) -> Slicer.  g.process(**{"in": x}) returns {"SlicerBlock": bits}."""
+    ClockSampler(baudrate) -> Slicer.  g.process(**{"in": x}) returns {"SlicerBlock": bits}; with framer=True the graph ends in
+    POCSAGFramerBlock and returns {"frames": types.POCSAGFrameType records}."""
     from .graph import DeviceGraph
     g = DeviceGraph()
     src = g.input("in", types.ComplexFloat32, rate)
@@ -566,7 +571,11 @@ def pocsag_receiver(rate=1e6, tune_offset=-100e3, baudrate=1200):
     g.connect(tuner, mark_filter, mark_magnitude)
     g.connect(mark_magnitude, "out", subtractor, "in1")
     g.connect(space_magnitude, "out", subtractor, "in2")
-    g.connect(subtractor, B.LowpassFilterBlock(128, baudrate), B.ClockSamplerBlock(baudrate), B.SlicerBlock())
+    tail = [B.LowpassFilterBlock(128, baudrate), B.ClockSamplerBlock(baudrate), B.SlicerBlock()]
+    if framer:
+        tail.append(B.POCSAGFramerBlock())
+        tail[-1].name = "frames"                   # the key of the output in process()'s result
+    g.connect(subtractor, *tail)
     return g.initialize()
 
 

@@ -29,6 +29,8 @@
 #include "kernels_preamble.h"
 #include "kernels_rdsframer.h"
 #include "kernels_ertframer.h"
+#include "kernels_ax25framer.h"
+#include "kernels_pocsagframer.h"
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
 #include "kernels_pll.h"
@@ -61,6 +63,8 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_preamble.h"
 #include "stage_rdsframer.h"
 #include "stage_ertframer.h"
+#include "stage_ax25framer.h"
+#include "stage_pocsagframer.h"
 #include "stage_modulator.h"
 #include "chain_plan.h"
 
@@ -417,6 +421,9 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "scmframer") return ertframer_create<EF_SCM>(op);
         if (head == "scmplusframer") return ertframer_create<EF_SCMPLUS>(op);
         if (head == "idmframer") return ertframer_create<EF_IDM>(op);
+        // nor the two packet framers (stage_ax25framer.h, stage_pocsagframer.h)
+        if (head == "ax25framer") return ax25framer_create(op);
+        if (head == "pocsagframer") return pocsagframer_create(op);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

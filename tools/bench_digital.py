@@ -3,8 +3,9 @@
 decoder chain and the clock recovery alone, on resident Float32 samples; the binary phase corrector (kernels_phasecorr.h) alone on resident
 ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the three digital receivers up to their bit streams.  HIP-event timing on the launch stream after warm-up, as
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
-(4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators and --ert-framers print the rows of the PAM / QAM modulators and
-of the SCM / SCM+ / IDM framers instead (modulator_rows, ert_framer_rows)."""
+(4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
+PAM / QAM modulators, of the SCM / SCM+ / IDM framers and of the AX.25 / POCSAG framers instead (modulator_rows, ert_framer_rows,
+packet_framer_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -22,12 +23,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--modulators", action="store_true", help="only the PAM / QAM modulator rows (profiles/modulator_table.jsonl)")
     ap.add_argument("--ert-framers", action="store_true", help="only the SCM / SCM+ / IDM framer rows (profiles/ert_framer_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --ert-framers: append the rows to this file as well")
+    ap.add_argument("--packet-framers", action="store_true", help="only the AX.25 / POCSAG framer rows (profiles/packet_framer_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --ert-framers / --packet-framers: append the rows to this file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
     if args.ert_framers:
         return ert_framer_rows(args)
+    if args.packet_framers:
+        return packet_framer_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -227,6 +231,70 @@ def ert_framer_rows(args):
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+
+
+def packet_framer_rows(args):
+    """AX25FramerBlock and POCSAGFramerBlock (kernels_ax25framer.h, kernels_pocsagframer.h) on 2^log2-samples resident Bit bytes, two inputs
+    each: random bits, and back-to-back frames (AX.25: flag, frame, flag with 0 .. 39 payload octets; POCSAG: batches of messages of 0 .. 6 data
+    words, the builders of tests/helpers/ax25_model.py and pocsag_model.py) - each next to a read-only pass over the same bytes (torch's sum), the
+    two alternating three times.  A call includes the framer's one count read-back.  A record, not an acceptance criterion.  --out appends the
+    rows to a file (profiles/packet_framer_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+    from tests.helpers import ax25_model as A
+    from tests.helpers import pocsag_model as P
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+    n = 1 << args.log2_samples
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    def tiled(pieces):
+        out = np.concatenate(pieces)
+        return np.tile(out, -(-n // len(out)))[:n]
+    inputs = {
+        (lr.AX25FramerBlock, "frames"): tiled([A.framed(A.random_octets(rng)) for _ in range(64)]),
+        (lr.POCSAGFramerBlock, "frames"): tiled([P.transmission(P.random_messages(rng, 40))[0]]),
+    }
+    for cls, frame_type in ((lr.AX25FramerBlock, types.AX25FrameType), (lr.POCSAGFramerBlock, types.POCSAGFrameType)):
+        for kind in ("random", "frames"):
+            bits = rng.integers(0, 2, n).astype(np.uint8) if kind == "random" else inputs[(cls, kind)]
+            x = torch.from_numpy(bits).cuda()
+            blk = cls()
+            blk.rate = 1200.0
+            blk.differentiate([types.Bit])
+            blk.initialize()
+            cap = blk.max_output(n)
+            y = torch.empty(cap * frame_type.dtype.itemsize + 64, dtype=torch.uint8, device="cuda")
+            count = []
+
+            def call():                               # successive calls continue one stream (the carried bytes of the call before)
+                count.append(blk.process_device(x.data_ptr(), n, y.data_ptr(), cap))
+            ms, ms_read = [], []
+            for _ in range(3):
+                ms.append(timed(call))
+                ms_read.append(timed(lambda: x.sum()))
+            row = {"row": "%s %s" % (cls.name, kind), "bits": n, "records_found": int(count[-1]), "ms": ms, "read_only_ms": ms_read,
+                   "share_of_read_only": round(min(ms_read) / min(ms), 3), "Gbit/s": round(n / min(ms) / 1e6, 2)}
+            line = json.dumps(row)
+            print(line)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
 
 
 if __name__ == "__main__":
