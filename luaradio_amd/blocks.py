@@ -916,7 +916,7 @@ class RDSFramerBlock(Block):
 
 
 class _ERTFramerBlock(Block):
-    """The three ERT framers (luaradio_amd/csrc/stage_ertframer.h): Bit -> one structured record per frame.  They follow the reference's
+    """The three ERT framers (luaradio_amd/csrc/stage_framers.h): Bit -> one structured record per frame.  They follow the reference's
     process() loops literally, the single-bit correction made inside the shift buffer included: a window that corrects a bit and then fails a
     later check leaves the flip behind for the windows after it.  The output count depends on the data; process(x) returns a structured array
     of the block's frame type, whose fields carry the reference's names."""
@@ -958,7 +958,7 @@ class IDMFramerBlock(_ERTFramerBlock):
 
 
 class _PacketFramerBlock(_ERTFramerBlock):
-    """The two packet framers (luaradio_amd/csrc/stage_ax25framer.h, stage_pocsagframer.h): Bit -> one fixed record per frame, whose type's
+    """The two packet framers (luaradio_amd/csrc/stage_framers.h): Bit -> one fixed record per frame, whose type's
     frames() gives the reference's variable-length objects back."""
 
 

@@ -373,9 +373,10 @@ static int digital_fuse_tail(std::vector<lrhip_chain::Op> &ops)
         f->in_size = 4; f->out_size = 1;
         if (f->reset()) return -1;
         // carried state: the clocksampler's, plus the decoder's previous input bit
-        LR_HIP(hipMemcpyAsync((DgState *)f->state.p, (const DgState *)cs->state.p + cs->cur, sizeof(DgState), hipMemcpyDeviceToDevice, ctx().stream));
-        if (dd) LR_HIP(hipMemcpyAsync(&((DgState *)f->state.p)->bit, (const uint8_t *)dd->state.p + dd->cur, 1, hipMemcpyDeviceToDevice, ctx().stream));
-        if (dd) LR_HIP(hipMemsetAsync((char *)&((DgState *)f->state.p)->bit + 1, 0, sizeof(int) - 1, ctx().stream));
+        DgState *fs = (DgState *)f->st.in();                 // what the fused stage's first call reads
+        LR_HIP(hipMemcpyAsync(fs, cs->st.in(), sizeof(DgState), hipMemcpyDeviceToDevice, ctx().stream));
+        if (dd) LR_HIP(hipMemcpyAsync(&fs->bit, (const uint8_t *)dd->state.p + dd->cur, 1, hipMemcpyDeviceToDevice, ctx().stream));
+        if (dd) LR_HIP(hipMemsetAsync((char *)&fs->bit + 1, 0, sizeof(int) - 1, ctx().stream));
         ops.erase(ops.begin() + (long)k + 1, ops.begin() + (long)k + (dd ? 3 : 2));
         ops[k] = lrhip_chain::Op(std::move(f));
     }

@@ -31,7 +31,7 @@
 // last 7 or fewer bytes no flag has consumed.  The bytes are carried raw: their values matter beyond `== 1`.
 #pragma once
 #include "common.h"
-#include "kernels_preamble.h"
+#include "kernels_bitscan.h"
 
 namespace lrhip {
 
@@ -63,31 +63,19 @@ struct AxState {
     unsigned long long nflags;       // consumed flags of the last call
 };
 
-// byte u of "carried bytes, then the call's bytes" (0 <= u < carry + n)
-struct AxRaw {
-    const uint8_t *__restrict__ x, *__restrict__ carried;
-    int carry;
-    __device__ __forceinline__ unsigned operator()(long long u) const { return u < carry ? carried[u] : x[u - carry]; }
-};
-
 __global__ __launch_bounds__(256) void ax_match_kernel(const uint8_t *__restrict__ x, const uint8_t *__restrict__ carried, unsigned long n,
                                                        const AxState *__restrict__ si, unsigned long long *__restrict__ mask_f, int *__restrict__ tile_f)
 {
     __shared__ unsigned long long s_bits[PS_WORDS + 1];      // the tile and the 7 bits behind it
     __shared__ unsigned long long s_f[PS_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const AxRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n, base = (long long)blockIdx.x * PS_TILE;
-    for (int w = wave; w < PS_WORDS + 1; w += 4) {
-        const long long u = base + w * 64 + lane;
-        const unsigned long long word = __ballot(u < total && raw(u) == 1u);
-        if (lane == 0) s_bits[w] = word;
-    }
+    bs_pack(raw, base, total, PS_WORDS + 1, s_bits);
     __syncthreads();
     for (int w = wave; w < PS_WORDS; w += 4) {
         // the 8 bits from position 64 w + lane, bit k = the k-th received; only flags that end inside the stream: p + 8 <= total
-        const unsigned long long lo = s_bits[w], hi = s_bits[w + 1];
-        const unsigned r = (unsigned)(lane ? (lo >> lane) | (hi << (64 - lane)) : lo) & 0xffu;
+        const unsigned r = (unsigned)bs_window(s_bits, w, lane) & 0xffu;
         const unsigned long long f = __ballot(r == AX_FLAG && base + w * 64 + lane + 8 <= total);
         if (lane == 0) {
             s_f[w] = f;
@@ -95,12 +83,7 @@ __global__ __launch_bounds__(256) void ax_match_kernel(const uint8_t *__restrict
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        int first = -1;
-        for (int w = PS_WORDS - 1; w >= 0; w--)
-            if (s_f[w]) first = w * 64 + __ffsll((long long)s_f[w]) - 1;
-        tile_f[blockIdx.x] = first;
-    }
+    bs_store_tile<false>(s_f, mask_f, tile_f);
 }
 
 __global__ __launch_bounds__(256) void ax_walk_kernel(const unsigned long long *__restrict__ mask_f, const int *__restrict__ tile_f, unsigned long ntiles,
@@ -140,7 +123,7 @@ __global__ __launch_bounds__(256) void ax_walk_kernel(const unsigned long long *
 // One wave (a workgroup of 64) evaluates the segment of R raw bytes at u = s: ax25_unstuff_frame, ax25_validate_frame and ax25_extract_frame
 // (:113-216).  Every thread calls with the same arguments and gets the same answer.  With rec != nullptr a valid frame's record is written.
 // buf: AX_CARRY bytes, oct: AX_DATA bytes, rows: AX_CRC_ROWS entries, all LDS.
-__device__ bool ax_evaluate(const AxRaw &raw, long long s, long long R, int lane, uint8_t *buf, uint8_t *oct, const uint16_t *rows, uint32_t *rec)
+__device__ bool ax_evaluate(const BsStream &raw, long long s, long long R, int lane, uint8_t *buf, uint8_t *oct, const uint16_t *rows, uint32_t *rec)
 {
     if (R > AX_RAW_MAX || R < AX_MIN_BITS) return false;     // (unstuffing only shortens)
     __syncthreads();                                          // the previous segment's reads of buf and oct are done
@@ -226,7 +209,7 @@ __global__ __launch_bounds__(64) void ax_eval_kernel(const uint8_t *__restrict__
     const int lane = threadIdx.x;
     const unsigned long long nf = so->overflow ? 0ull : so->nflags;
     if (blockIdx.x >= nf) return;
-    const AxRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     for (int i = lane; i < AX_CRC_ROWS; i += 64) s_rows[i] = rows[i];
     __syncthreads();
     for (unsigned long long k = blockIdx.x; k < nf; k += gridDim.x) {
@@ -244,7 +227,7 @@ __global__ __launch_bounds__(256) void ax_select_kernel(const uint8_t *__restric
     __shared__ int s_to[2][256], s_in[256], s_last;
     __shared__ unsigned long long s_cnt[2][256], s_base[256], s_total;
     const int tid = threadIdx.x;
-    const AxRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n;
     const int failed = so->overflow;
     const unsigned long long nf = failed ? 0ull : so->nflags;
@@ -314,7 +297,7 @@ __global__ __launch_bounds__(64) void ax_emit_kernel(const uint8_t *__restrict__
     unsigned long long nframes = so->overflow ? 0ull : so->count;
     if (nframes > cap) nframes = cap;
     if (blockIdx.x >= nframes) return;
-    const AxRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     for (int i = lane; i < AX_CRC_ROWS; i += 64) s_rows[i] = rows[i];
     __syncthreads();
     for (unsigned long long f = blockIdx.x; f < nframes; f += gridDim.x) {

@@ -39,7 +39,7 @@
 // Carried between calls, ping-pong on the device: the effective bytes since q and EfState.
 #pragma once
 #include "common.h"
-#include "kernels_preamble.h"
+#include "kernels_bitscan.h"
 
 namespace lrhip {
 
@@ -53,14 +53,6 @@ template <int K> struct EfProto;
 template <> struct EfProto<EF_SCM> { static constexpr int L = 96, PRE = 21, CW = 75, REC = 16; static constexpr unsigned PATTERN = 0x1f2a60u, INIT = 0u; };
 template <> struct EfProto<EF_SCMPLUS> { static constexpr int L = 128, PRE = 16, CW = 112, REC = 16; static constexpr unsigned PATTERN = 0x16a3u, INIT = 0x7b06u; };
 template <> struct EfProto<EF_IDM> { static constexpr int L = 736, PRE = 32, CW = 704, REC = 88; static constexpr unsigned PATTERN = 0x555516a3u, INIT = 0x866bu; };
-
-// the preamble in stream order: bit k = the k-th byte received (PATTERN is MSB first)
-constexpr unsigned ef_stream_order(unsigned pattern, int bits)
-{
-    unsigned r = 0;
-    for (int k = 0; k < bits; k++) r |= ((pattern >> (bits - 1 - k)) & 1u) << k;
-    return r;
-}
 
 // idm_compute_crc (idmframer.lua:140-154) on byte values: (crc & 0x8000) ^ (b << 15) is compared with 0x8000, so a byte of 1 takes the XOR
 // branch when the top bit is clear, a byte of 0 when it is set, and a byte of 2 or more never does
@@ -103,23 +95,16 @@ struct EfState {
     unsigned long long count;        // frames of the last call
 };
 
-// byte u of "carried bytes, then the call's bytes" (0 <= u < carry + n)
-struct EfRaw {
-    const uint8_t *__restrict__ x, *__restrict__ carried;
-    int carry;
-    __device__ __forceinline__ unsigned operator()(long long u) const { return u < carry ? carried[u] : x[u - carry]; }
-};
-
 // byte i of the window that starts at u = s, raw
 struct EfWindow {
-    EfRaw raw;
+    BsStream raw;
     long long s;
     __device__ __forceinline__ unsigned operator()(int i) const { return raw(s + i); }
 };
 
 // byte i of the window that starts at u = s under the ring of pending flips: ring[u mod L] overrides byte u (at = s mod L, 0 <= i < L)
 template <int L> struct EfRing {
-    EfRaw raw;
+    BsStream raw;
     const uint8_t *ring;
     long long s;
     int at;
@@ -248,20 +233,16 @@ __global__ __launch_bounds__(256) void ef_match_kernel(const uint8_t *__restrict
     __shared__ uint16_t s_rows[P::CW];
     __shared__ int any;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const EfRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n, base = (long long)blockIdx.x * PS_TILE;
     if (tid == 0) any = 0;
-    for (int w = wave; w < PS_WORDS + 1; w += 4) {
-        const long long u = base + w * 64 + lane;
-        const unsigned long long word = __ballot(u < total && raw(u) == 1u);
-        if (lane == 0) s_bits[w] = word;
-    }
+    bs_pack(raw, base, total, PS_WORDS + 1, s_bits);
     __syncthreads();
     for (int w = wave; w < PS_WORDS; w += 4) {
-        // the PRE bits from start 64 w + lane, bit k = the k-th received; only windows that end inside the stream: s + L <= total
-        const unsigned long long lo = s_bits[w], hi = s_bits[w + 1];
-        const unsigned r = (unsigned)(lane ? (lo >> lane) | (hi << (64 - lane)) : lo) & (unsigned)((1ull << P::PRE) - 1ull);
-        const unsigned long long c = __ballot(r == ef_stream_order(P::PATTERN, P::PRE) && base + w * 64 + lane + P::L <= total);
+        // the PRE bits from start 64 w + lane, bit k = the k-th received (PATTERN is MSB first); only windows that end inside the stream:
+        // s + L <= total
+        const unsigned r = (unsigned)bs_window(s_bits, w, lane) & (unsigned)((1ull << P::PRE) - 1ull);
+        const unsigned long long c = __ballot(r == bs_stream_order(P::PATTERN, P::PRE) && base + w * 64 + lane + P::L <= total);
         if (lane == 0) {
             s_cand[w] = c;
             if (c) any = 1;
@@ -287,16 +268,8 @@ __global__ __launch_bounds__(256) void ef_match_kernel(const uint8_t *__restrict
         if (lane == 0) { s_event[w] = ev; s_accept[w] = ac; }
     }
     __syncthreads();
-    if (tid < PS_WORDS) {
-        mask_e[(unsigned long)blockIdx.x * PS_WORDS + tid] = s_event[tid];
-        mask_a[(unsigned long)blockIdx.x * PS_WORDS + tid] = s_accept[tid];
-    }
-    if (tid == 0) {
-        int first = -1;
-        for (int w = PS_WORDS - 1; w >= 0; w--)
-            if (s_event[w]) first = w * 64 + __ffsll((long long)s_event[w]) - 1;
-        tile_e[blockIdx.x] = first;
-    }
+    bs_store_tile(s_event, mask_e, tile_e);
+    if (tid < PS_WORDS) mask_a[(unsigned long)blockIdx.x * PS_WORDS + tid] = s_accept[tid];
 }
 
 template <int K>
@@ -311,7 +284,7 @@ __global__ __launch_bounds__(256) void ef_walk_kernel(const uint8_t *__restrict_
     __shared__ uint16_t s_rows[P::CW];
     __shared__ uint8_t s_ring[P::L];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const EfRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n;
     for (int i = tid; i < P::CW; i += 256) s_rows[i] = rows[i];
     for (int i = tid; i < P::L; i += 256) s_ring[i] = EF_NO_OVERRIDE;
@@ -322,12 +295,12 @@ __global__ __launch_bounds__(256) void ef_walk_kernel(const uint8_t *__restrict_
     // every thread runs the same automaton on the same values (each wave classifies for itself); thread 0 and wave 0 write
     while (q + P::L <= total) {
         long long s = q;
-        if (!((mask_e[q >> 6] >> (q & 63)) & 1ull)) {
+        if (!bs_test(mask_e, q)) {
             s = ps_find_first(mask_e, tile_e, ntiles, q, &s_res);
             if (s == PS_NONE) { q = total - (P::L - 1); break; }         // every window up to total - L was rejected without a trace
         }
         if (nframes >= max_frames) { overflow = 1; break; }
-        if ((mask_a[s >> 6] >> (s & 63)) & 1ull) {
+        if (bs_test(mask_a, s)) {
             if (tid == 0) starts[nframes] = s;
             nframes++;
             q = s + P::L;
@@ -395,7 +368,7 @@ __global__ __launch_bounds__(256) void ef_emit_kernel(const uint8_t *__restrict_
     if (f >= nframes || f >= cap) return;
     const long long s = starts[f];
     if (s < 0) return;                                                    // accepted in literal mode: the walk has written it
-    const EfWindow win{EfRaw{x, carried, si->carry}, s};
+    const EfWindow win{BsStream{x, carried, si->carry}, s};
     int flip;
     ef_classify<K>(win, s_rows, lane, &flip);
     const EfCorrected<EfWindow> fixed{win, flip};

@@ -28,8 +28,7 @@
 //                    next call's slot.
 #pragma once
 #include "common.h"
-#include "kernels_preamble.h"
-#include "kernels_ertframer.h"
+#include "kernels_bitscan.h"
 
 namespace lrhip {
 
@@ -59,32 +58,20 @@ struct PgState {
     unsigned data[PG_WORDS];
 };
 
-struct PgRaw {
-    const uint8_t *__restrict__ x, *__restrict__ carried;
-    int carry;
-    __device__ __forceinline__ unsigned operator()(long long u) const { return u < carry ? carried[u] : x[u - carry]; }
-};
-
 __global__ __launch_bounds__(256) void pg_match_kernel(const uint8_t *__restrict__ x, const uint8_t *__restrict__ carried, unsigned long n,
                                                        const PgState *__restrict__ si, unsigned long long *__restrict__ mask_s, int *__restrict__ tile_s)
 {
     __shared__ unsigned long long s_bits[PS_WORDS + 1], s_big[PS_WORDS + 1];      // the tile and the 31 positions behind it
     __shared__ unsigned long long s_s[PS_WORDS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PgRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n, base = (long long)blockIdx.x * PS_TILE;
-    for (int w = wave; w < PS_WORDS + 1; w += 4) {
-        const long long u = base + w * 64 + lane;
-        const unsigned b = u < total ? raw(u) : 0u;
-        const unsigned long long one = __ballot(b == 1u), big = __ballot(b > 1u);
-        if (lane == 0) { s_bits[w] = one; s_big[w] = big; }
-    }
+    bs_pack<true>(raw, base, total, PS_WORDS + 1, s_bits, s_big);
     __syncthreads();
-    constexpr unsigned SYNC = ef_stream_order(PG_SYNC_CODEWORD, 32);             // bit k = the k-th byte received
+    constexpr unsigned SYNC = bs_stream_order(PG_SYNC_CODEWORD, 32);             // bit k = the k-th byte received
     for (int w = wave; w < PS_WORDS; w += 4) {
         const long long p = base + w * 64 + lane;
-        const unsigned r = (unsigned)(lane ? (s_bits[w] >> lane) | (s_bits[w + 1] << (64 - lane)) : s_bits[w]);
-        const unsigned g = (unsigned)(lane ? (s_big[w] >> lane) | (s_big[w + 1] << (64 - lane)) : s_big[w]);
+        const unsigned r = (unsigned)bs_window(s_bits, w, lane), g = (unsigned)bs_window(s_big, w, lane);
         bool hit = false;
         if (p + PG_CODEWORD <= total) {
             if (!g) {
@@ -102,12 +89,7 @@ __global__ __launch_bounds__(256) void pg_match_kernel(const uint8_t *__restrict
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        int first = -1;
-        for (int w = PS_WORDS - 1; w >= 0; w--)
-            if (s_s[w]) first = w * 64 + __ffsll((long long)s_s[w]) - 1;
-        tile_s[blockIdx.x] = first;
-    }
+    bs_store_tile<false>(s_s, mask_s, tile_s);
 }
 
 // pocsag_correct_codeword (:120-149).  Returns false when the codeword is uncorrectable.
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(256) void pg_walk_kernel(const uint8_t *__restrict_
     __shared__ unsigned s_data[PG_WORDS], s_cw[17];
     __shared__ int s_ok[17];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const PgRaw raw{x, carried, si->carry};
+    const BsStream raw{x, carried, si->carry};
     const long long total = (long long)raw.carry + (long long)n;
     int mode = si->mode, has = si->has;
     unsigned address = si->address, func = si->func, flags = si->flags, count = si->count;

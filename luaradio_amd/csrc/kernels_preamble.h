@@ -18,7 +18,7 @@
 //                    addresses.  Traffic: 4 B per sample and tap actually read (the taps of one sample are T samples apart, so nothing is
 //                    shared between them; other waves re-read the same lines from L2) - on random signs two taps per lane, 8 B per sample,
 //                    while a wave of 64 stays in the loop for about seven taps.
-//   ps_walk_kernel   ONE workgroup hops from frame to frame.  "first set bit at or after p" scans the mask words of p's tile (16 lanes, one
+//   ps_walk_kernel   ONE workgroup hops from frame to frame.  "first set bit at or after p" (ps_find_first, kernels_bitscan.h) scans the mask words of p's tile (16 lanes, one
 //                    word each) and from the next tile on the tile summaries, 256 tiles per step by the whole workgroup.  Serial cost: one hop (two searches of two barriers and one round of loads each, about 2 us) per frame
 //                    plus O(tiles / 256) search steps in total - a stretch without a match or a long non-degrading run costs
 //                    tiles / 256 steps, not samples.  Writes the frame list (j*, output base, first m, last m inside this call), the
@@ -34,11 +34,9 @@
 #pragma once
 #include "common.h"
 #include "kernels_digital.h"
+#include "kernels_bitscan.h"
 
 namespace lrhip {
-
-constexpr int PS_TILE = 1024, PS_WORDS = PS_TILE / 64;      // samples and mask words per tile (one workgroup of 256 threads, 4 samples each)
-constexpr long long PS_NONE = 0x7fffffffffffffffll;
 
 enum { PS_SEARCHING = 0, PS_OPTIMIZING = 1, PS_SAMPLING = 2 };
 
@@ -117,38 +115,6 @@ __global__ __launch_bounds__(256) void ps_match_kernel(const float *__restrict__
         tile_m[blockIdx.x] = first_m < PS_TILE ? first_m : -1;
         tile_d[blockIdx.x] = first_d < PS_TILE ? first_d : -1;
     }
-}
-
-// first set bit at or after `from` (call-relative sample, from < ntiles * PS_TILE), or PS_NONE.  Called by all 256 threads with equal arguments;
-// every thread gets the same answer.
-__device__ long long ps_find_first(const unsigned long long *__restrict__ words, const int *__restrict__ tsum, unsigned long ntiles, long long from,
-                                   unsigned long long *s_res)
-{
-    const int tid = threadIdx.x;
-    const unsigned long tile = (unsigned long)(from / PS_TILE);
-    if (tid == 0) *s_res = (unsigned long long)PS_NONE;  // (every read of *s_res below is followed by a barrier)
-    __syncthreads();
-    if (tid < PS_WORDS) {
-        const long long lo = (long long)tile * PS_TILE + tid * 64;
-        unsigned long long w = words[tile * PS_WORDS + tid];
-        if (from >= lo + 64) w = 0;
-        else if (from > lo) w &= ~0ull << (from - lo);
-        if (w) atomicMin(s_res, (unsigned long long)(lo + __ffsll((long long)w) - 1));
-    }
-    __syncthreads();
-    long long r = (long long)*s_res;
-    __syncthreads();
-    // (the summaries only after the own tile has failed.  Both in one step was slower, 4.3 against 2.0 ms per 2^24 samples with a frame every
-    // 20 000: nearly every tile has a "first D", so all 256 lanes then update the one LDS word)
-    for (unsigned long t0 = tile + 1; r == PS_NONE && t0 < ntiles; t0 += 256) {
-        const unsigned long t = t0 + tid;
-        const int f = t < ntiles ? tsum[t] : -1;
-        if (f >= 0) atomicMin(s_res, (unsigned long long)((long long)t * PS_TILE + f));
-        __syncthreads();
-        r = (long long)*s_res;
-        __syncthreads();
-    }
-    return r;
 }
 
 __global__ __launch_bounds__(256) void ps_walk_kernel(const unsigned long long *__restrict__ mask_m, const unsigned long long *__restrict__ mask_d,

@@ -13,7 +13,7 @@
 // and from the first unconsumed bit q the walk takes the first s >= q with V(s), emits it and sets q = s + 104: a valid window that starts inside an
 // accepted frame is never emitted.
 //
-// Passes (3 launches, one count read-back), the shape of kernels_preamble.h:
+// Passes (3 launches, one count read-back), the shape of kernels_bitscan.h:
 //   rf_match_kernel  one workgroup per tile of PS_TILE window starts.  The `== 1` bytes of the tile and of the 192 bits behind it are packed into
 //                    64-bit words by wave ballots (LDS); each lane then takes one block start, computes S by 26 conditional XORs of immediates on
 //                    the funnel-shifted window and looks its four flags up in the LDS copy of the table; four ballots give the flag masks, and V
@@ -29,7 +29,7 @@
 // Carried between calls, ping-pong on the device: the bits since q (at most 103: every window that ends inside a call is tested in it) and RfState.
 #pragma once
 #include "common.h"
-#include "kernels_preamble.h"
+#include "kernels_bitscan.h"
 
 namespace lrhip {
 
@@ -66,12 +66,6 @@ struct RfState {
     unsigned long long count;        // frames of the last call
 };
 
-// bit u of "carried bits, then the call's bits" (0 <= u < carry + n)
-__device__ __forceinline__ unsigned rf_bit(const uint8_t *__restrict__ x, const uint8_t *__restrict__ carried, int carry, long long u)
-{
-    return (u < carry ? carried[u] : x[u - carry]) == 1 ? 1u : 0u;
-}
-
 // syndrome of a block given in stream order: bit k of r = bit k of the block as received
 __device__ __forceinline__ unsigned rf_syndrome(unsigned r)
 {
@@ -86,24 +80,17 @@ __global__ __launch_bounds__(256) void rf_match_kernel(const uint8_t *__restrict
                                                        unsigned long long *__restrict__ mask_v, int *__restrict__ tile_v)
 {
     __shared__ unsigned long long s_bits[RF_BIT_WORDS];
-    __shared__ unsigned long long s_flag[4][RF_FLAG_WORDS];
+    __shared__ unsigned long long s_flag[4][RF_FLAG_WORDS], s_v[PS_WORDS];
     __shared__ __attribute__((aligned(16))) uint8_t s_table[1024];
-    __shared__ int first_v;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int carry = si->carry;
-    const long long total = (long long)carry + (long long)n, base = (long long)blockIdx.x * PS_TILE;
+    const BsStream in{x, carried, si->carry};
+    const long long total = (long long)in.carry + (long long)n, base = (long long)blockIdx.x * PS_TILE;
     ((uint32_t *)s_table)[tid] = ((const uint32_t *)table)[tid];
-    if (tid == 0) first_v = PS_TILE;
-    for (int w = wave; w < RF_BIT_WORDS; w += 4) {
-        const long long u = base + w * 64 + lane;
-        const unsigned long long word = __ballot(u < total && rf_bit(x, carried, carry, u));
-        if (lane == 0) s_bits[w] = word;
-    }
+    bs_pack(in, base, total, RF_BIT_WORDS, s_bits);
     __syncthreads();
     for (int w = wave; w < RF_FLAG_WORDS; w += 4) {
         // the 26 bits from block start b = 64 w + lane, bit k = the k-th received (w + 1 < RF_BIT_WORDS)
-        const unsigned long long lo = s_bits[w], hi = s_bits[w + 1];
-        const unsigned r = (unsigned)(lane ? (lo >> lane) | (hi << (64 - lane)) : lo) & ((1u << RF_BLOCK) - 1u);
+        const unsigned r = (unsigned)bs_window(s_bits, w, lane) & ((1u << RF_BLOCK) - 1u);
         const unsigned f = s_table[rf_syndrome(r)];
         const unsigned long long fa = __ballot(f & RF_FLAG_A), fb = __ballot(f & RF_FLAG_B), fc = __ballot(f & RF_FLAG_C), fd = __ballot(f & RF_FLAG_D);
         if (lane == 0) { s_flag[0][w] = fa; s_flag[1][w] = fb; s_flag[2][w] = fc; s_flag[3][w] = fd; }
@@ -120,10 +107,10 @@ __global__ __launch_bounds__(256) void rf_match_kernel(const uint8_t *__restrict
         if (last < lo) v = 0;
         else if (last < lo + 63) v &= ~0ull >> (63 - (last - lo));
         mask_v[(unsigned long)blockIdx.x * PS_WORDS + tid] = v;
-        if (v) atomicMin(&first_v, tid * 64 + __ffsll((long long)v) - 1);
+        s_v[tid] = v;
     }
     __syncthreads();
-    if (tid == 0) tile_v[blockIdx.x] = first_v < PS_TILE ? first_v : -1;
+    bs_store_tile<false>(s_v, mask_v, tile_v);
 }
 
 __global__ __launch_bounds__(256) void rf_walk_kernel(const unsigned long long *__restrict__ mask_v, const int *__restrict__ tile_v, unsigned long ntiles,
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(256) void rf_walk_kernel(const unsigned long long *
     // every thread runs the same automaton on the same values; thread 0 writes
     while (q + RF_FRAME <= total) {
         long long s = q;
-        if (!((mask_v[q >> 6] >> (q & 63)) & 1ull)) {
+        if (!bs_test(mask_v, q)) {
             s = ps_find_first(mask_v, tile_v, ntiles, q, &s_res);
             if (s == PS_NONE) { q = total - (RF_FRAME - 1); break; }      // every window up to total - 104 was rejected
         }
@@ -170,7 +157,7 @@ __global__ __launch_bounds__(256) void rf_emit_kernel(const uint8_t *__restrict_
                                                       unsigned long n, const RfState *__restrict__ si, const RfState *__restrict__ so,
                                                       const long long *__restrict__ starts, unsigned long long *__restrict__ y, unsigned long cap)
 {
-    const int carry = si->carry;
+    const BsStream in{x, carried, si->carry};
     const unsigned long long nframes = so->overflow ? 0ull : so->count;
     const unsigned long long f = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
     if (f < nframes && f < cap) {
@@ -179,7 +166,7 @@ __global__ __launch_bounds__(256) void rf_emit_kernel(const uint8_t *__restrict_
 #pragma unroll 1
         for (int b = 0; b < 4; b++) {
             unsigned r = 0;
-            for (int k = 0; k < RF_BLOCK; k++) r |= rf_bit(x, carried, carry, s + b * RF_BLOCK + k) << k;
+            for (int k = 0; k < RF_BLOCK; k++) r |= (unsigned)in.one(s + b * RF_BLOCK + k) << k;
             int v = rf_correct(r, b == 0 ? RF_OFFSET_A : b == 1 ? RF_OFFSET_B : b == 2 ? RF_OFFSET_C : RF_OFFSET_D);
             if (b == 2 && v < 0) v = rf_correct(r, RF_OFFSET_CP);
             rec |= (unsigned long long)(((unsigned)v >> 10) & 0xffffu) << (16 * b);       // blocks[b], little-endian
@@ -188,8 +175,9 @@ __global__ __launch_bounds__(256) void rf_emit_kernel(const uint8_t *__restrict_
     }
     if (blockIdx.x == 0 && !so->overflow) {
         const int next = so->carry;                          // <= 103 < RF_CARRY
-        const long long total = (long long)carry + (long long)n;
-        if ((int)threadIdx.x < next) carried_out[threadIdx.x] = (uint8_t)rf_bit(x, carried, carry, total - next + threadIdx.x);
+        const long long total = (long long)in.carry + (long long)n;
+        // (carried as 0 / 1, where the other framers carry raw bytes: every read of this slot goes through `== 1`)
+        if ((int)threadIdx.x < next) carried_out[threadIdx.x] = (uint8_t)in.one(total - next + threadIdx.x);
     }
 }
 

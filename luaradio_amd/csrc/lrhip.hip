@@ -26,6 +26,7 @@
 #include "kernels_interp.h"
 #include "kernels_rx.h"
 #include "kernels_digital.h"
+#include "kernels_bitscan.h"
 #include "kernels_preamble.h"
 #include "kernels_rdsframer.h"
 #include "kernels_ertframer.h"
@@ -46,6 +47,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
     } while (0)
 
 #include "stage.h"
+#include "stage_counted.h"
 #include "stage_fir.h"
 #include "stage_elem.h"
 #include "stage_iir.h"
@@ -61,10 +63,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_digital.h"
 #include "stage_pll.h"
 #include "stage_preamble.h"
-#include "stage_rdsframer.h"
-#include "stage_ertframer.h"
-#include "stage_ax25framer.h"
-#include "stage_pocsagframer.h"
+#include "stage_framers.h"
 #include "stage_modulator.h"
 #include "chain_plan.h"
 
@@ -415,15 +414,13 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "pam" || head == "qam") return modulator_create(op);
         // the PLL names its output port in words (stage_pll.h)
         if (head == "pll") return pll_create(op);
-        // the RDS framer takes no parameters at all (stage_rdsframer.h)
-        if (head == "rdsframer") return rdsframer_create(op);
-        // nor do the three ERT framers (stage_ertframer.h)
-        if (head == "scmframer") return ertframer_create<EF_SCM>(op);
-        if (head == "scmplusframer") return ertframer_create<EF_SCMPLUS>(op);
-        if (head == "idmframer") return ertframer_create<EF_IDM>(op);
-        // nor the two packet framers (stage_ax25framer.h, stage_pocsagframer.h)
-        if (head == "ax25framer") return ax25framer_create(op);
-        if (head == "pocsagframer") return pocsagframer_create(op);
+        // the five framers take no parameters at all (stage_framers.h)
+        if (head == "rdsframer") return plain_create<RfStage>(op, 8);
+        if (head == "scmframer") return plain_create<EfStage<EF_SCM>>(op, EfProto<EF_SCM>::REC);
+        if (head == "scmplusframer") return plain_create<EfStage<EF_SCMPLUS>>(op, EfProto<EF_SCMPLUS>::REC);
+        if (head == "idmframer") return plain_create<EfStage<EF_IDM>>(op, EfProto<EF_IDM>::REC);
+        if (head == "ax25framer") return plain_create<AxStage>(op, AX_REC);
+        if (head == "pocsagframer") return plain_create<PgStage>(op, PG_REC);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

@@ -67,13 +67,13 @@ static void zc_prepare(double P, double T, ZcParams &p)
     p.closed = 1;
 }
 
-static int dg_state_init(DeviceBuf &state, double P = 0.0)
+static DgState dg_state_init(double P = 0.0)
 {
-    DgState s[2];
-    memset(s, 0, sizeof(s));
-    s[0].h = s[1].h = -1;                                    // hysteresis false / clock LOW
-    s[0].o = s[1].o = P;                                     // zerocrossingclockrecovery.lua:37: the offset starts at one symbol period
-    return upload(state, s, sizeof(s));
+    DgState s;
+    memset(&s, 0, sizeof(s));
+    s.h = -1;                                                // hysteresis false / clock LOW
+    s.o = P;                                                 // zerocrossingclockrecovery.lua:37: the offset starts at one symbol period
+    return s;
 }
 
 // =====================================================================================================
@@ -83,30 +83,26 @@ struct ZcStage : lrhip_stage {
     ZcParams p;
     bool sampler = false;                    // clocksampler: emits x[i] where the recovered clock rises
     DgTail tail{DG_OUT_FLOAT, 0.0, 0};
-    DeviceBuf state, scratch, staging;
-    PinnedBuf h_count;
-    int cur = 0;
+    DeviceBuf scratch, staging;
+    Carried<DgState> st;
     const char *kind() const override { return sampler ? "clocksampler" : "zerocrossingclockrecovery"; }
     long memory() const override { return -1; }
-    int reset() override { cur = 0; return dg_state_init(state, p.P); }
+    int reset() override { return st.reset(dg_state_init(p.P)); }
     unsigned long max_output(unsigned long n) const override { return sampler ? (n + 1) / 2 + 1 : n; }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
         if (!sampler && n > cap) return set_error("%s: output capacity %lu < %lu", kind(), cap, n);
         if (!n) return 0;
         const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
-        // scratch: tile summaries, then per-tile h, rpos, kind, literal offset, previous clock, count, last bit
-        const size_t o_h = nt * sizeof(HSum), o_rpos = o_h + nt * 8, o_kind = o_rpos + nt * 8, o_o = o_kind + nt * 8, o_prev = o_o + nt * 8,
-                     o_cnt = o_prev + nt * 8, o_bit = o_cnt + nt * 8, total = o_bit + nt * 8;
-        if (scratch.reserve(total)) return -1;
-        char *sp = (char *)scratch.p;
-        HSum *tiles = (HSum *)sp;
-        int *t_h = (int *)(sp + o_h), *t_kind = (int *)(sp + o_kind), *t_prev = (int *)(sp + o_prev), *t_bit = (int *)(sp + o_bit);
-        long long *t_rpos = (long long *)(sp + o_rpos);
-        double *t_o = (double *)(sp + o_o);
-        unsigned *t_cnt = (unsigned *)(sp + o_cnt);
-        const DgState *si = (const DgState *)state.p + cur;
-        DgState *so = (DgState *)state.p + (cur ^ 1);
+        const ZcScratch sc(nt);
+        if (scratch.reserve(sc.total)) return -1;
+        HSum *tiles = sc.tiles.in(scratch);
+        int *t_h = sc.t_h.in(scratch), *t_kind = sc.t_kind.in(scratch), *t_prev = sc.t_prev.in(scratch), *t_bit = sc.t_bit.in(scratch);
+        long long *t_rpos = sc.t_rpos.in(scratch);
+        double *t_o = sc.t_o.in(scratch);
+        unsigned *t_cnt = sc.t_cnt.in(scratch);
+        const DgState *si = st.in();
+        DgState *so = st.out();
         const float *x = (const float *)in_dev;
         hipLaunchKernelGGL(zc_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, p.T, tiles);
         LR_LAUNCH_CHECK();
@@ -116,7 +112,7 @@ struct ZcStage : lrhip_stage {
             hipLaunchKernelGGL((zc_emit_kernel<0>), dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, p, tail, out_dev, si, so,
                                (const int *)t_h, (const long long *)t_rpos, (const int *)t_kind, (const double *)t_o, (const int *)t_prev, t_cnt, t_bit);
             LR_LAUNCH_CHECK();
-            cur ^= 1;
+            st.flip();
             return (long)n;
         }
         const unsigned long bound = max_output(n);
@@ -139,14 +135,11 @@ struct ZcStage : lrhip_stage {
             hipLaunchKernelGGL((dg_compact_kernel<DG_OUT_DECODE>), dim3((unsigned)groups), dim3(256), 0, ctx().stream, (const void *)staging.p, (const unsigned *)t_cnt,
                                (const int *)t_bit, nt, per, tail, out_dev, cap, si, so);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        // the data-dependent count: the one small read-back of this stage
-        if (h_count.reserve(sizeof(unsigned long long))) return -1;
-        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
-        LR_HIP(hipStreamSynchronize(ctx().stream));
-        const unsigned long long got = *(const unsigned long long *)h_count.p;
-        if (got > bound) return set_error("%s: %llu outputs exceed the bound %lu", kind(), got, bound);
-        return (long)got;
+        st.flip();
+        DgState got;
+        if (st.fetch(got)) return -1;
+        if (got.count > bound) return set_error("%s: %llu outputs exceed the bound %lu", kind(), got.count, bound);
+        return (long)got.count;
     }
 };
 
@@ -154,12 +147,11 @@ struct ZcStage : lrhip_stage {
 // SamplerBlock: data (Float32 or ComplexFloat32) and clock (Float32) -> the data type, data-dependent count
 // =====================================================================================================
 struct SamplerStage : BinaryStage {
-    DeviceBuf state, scratch;
-    PinnedBuf h_count;
-    int cur = 0;
+    DeviceBuf scratch;
+    Carried<DgState> st;
     const char *kind() const override { return "sampler"; }
     long memory() const override { return -1; }
-    int reset() override { cur = 0; return dg_state_init(state); }
+    int reset() override { return st.reset(dg_state_init()); }
     unsigned long max_output(unsigned long n) const override { return (n + 1) / 2 + 1; }
     long run2(const void *data, const void *clk, unsigned long n, void *y, unsigned long cap) override
     {
@@ -167,14 +159,13 @@ struct SamplerStage : BinaryStage {
         const unsigned long bound = max_output(n);
         if (cap < bound) return set_error("sampler: output capacity %lu < bound %lu", cap, bound);
         const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
-        const size_t o_h = nt * sizeof(SSum), o_off = o_h + nt * 8, total = o_off + nt * 8;
-        if (scratch.reserve(total)) return -1;
-        char *sp = (char *)scratch.p;
-        SSum *tiles = (SSum *)sp;
-        int *t_h = (int *)(sp + o_h);
-        unsigned long long *t_off = (unsigned long long *)(sp + o_off);
-        const DgState *si = (const DgState *)state.p + cur;
-        DgState *so = (DgState *)state.p + (cur ^ 1);
+        const SamplerScratch sc(nt);
+        if (scratch.reserve(sc.total)) return -1;
+        SSum *tiles = sc.tiles.in(scratch);
+        int *t_h = sc.t_h.in(scratch);
+        unsigned long long *t_off = sc.t_off.in(scratch);
+        const DgState *si = st.in();
+        DgState *so = st.out();
         hipLaunchKernelGGL(sampler_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, (const float *)clk, n, tiles);
         LR_LAUNCH_CHECK();
         hipLaunchKernelGGL(sampler_carry_kernel, dim3(1), dim3(256), 0, ctx().stream, (const SSum *)tiles, nt, si, so, t_h, t_off);
@@ -186,13 +177,11 @@ struct SamplerStage : BinaryStage {
             hipLaunchKernelGGL(sampler_final_kernel<1>, dim3((unsigned)nt), dim3(256), 0, ctx().stream, (const float *)data, (const float *)clk, n, (float *)y, cap,
                                (const int *)t_h, (const unsigned long long *)t_off);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        if (h_count.reserve(sizeof(unsigned long long))) return -1;
-        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
-        LR_HIP(hipStreamSynchronize(ctx().stream));
-        const unsigned long long got = *(const unsigned long long *)h_count.p;
-        if (got > bound) return set_error("sampler: %llu outputs exceed the bound %lu", got, bound);
-        return (long)got;
+        st.flip();
+        DgState got;
+        if (st.fetch(got)) return -1;
+        if (got.count > bound) return set_error("sampler: %llu outputs exceed the bound %lu", got.count, bound);
+        return (long)got.count;
     }
 };
 

@@ -14,17 +14,13 @@ constexpr long long PS_MAX_B = 1ll << 21;
 struct PsStage : lrhip_stage {
     PsParams p{0, 0, 0, 0};
     std::vector<uint32_t> pre_bits;          // the preamble, bit k of word k / 32
-    DeviceBuf pre, state, hist, scratch;     // state: two PsState; hist: two histories of B samples (ping-pong with `cur`)
-    PinnedBuf h_state;
-    int cur = 0;
+    DeviceBuf pre, hist, scratch;            // hist: two histories of B samples, alternating with st.cur
+    Carried<PsState> st;                     // SEARCHING, preamblesampler.lua:56-59
     const char *kind() const override { return "preamblesampler"; }
     long memory() const override { return -1; }
     int reset() override
     {
-        cur = 0;
-        PsState s[2];
-        memset(s, 0, sizeof(s));                             // SEARCHING, preamblesampler.lua:56-59
-        if (upload(pre, pre_bits.data(), pre_bits.size() * sizeof(uint32_t)) || upload(state, s, sizeof(s))) return -1;
+        if (upload(pre, pre_bits.data(), pre_bits.size() * sizeof(uint32_t)) || st.reset()) return -1;
         return zero_fill(hist, 2 * (size_t)p.B * sizeof(float));      // the reference's buffer starts as zeros (:52)
     }
     // Output 0 of a frame is emitted at sample j*, output m >= 1 at j* + m T - 1: inside a frame consecutive emissions are T - 1 (m = 0 -> 1) or
@@ -41,17 +37,15 @@ struct PsStage : lrhip_stage {
         // frames with an output inside one call: the j* of consecutive frames are at least (N - 1) T + 2 samples apart, so at most
         // n / ((N - 1) T) + 1 of them lie inside the call, plus the frame in progress at its start
         const unsigned long max_frames = n / ((unsigned long)(p.N - 1) * (unsigned long)p.T) + 2;
-        const size_t words = (size_t)nt * PS_WORDS * 8, o_md = words, o_tm = 2 * words, o_td = o_tm + (size_t)nt * 4,
-                     o_fr = (o_td + (size_t)nt * 4 + 15) / 16 * 16, total = o_fr + max_frames * sizeof(PsFrame);
-        if (scratch.reserve(total) || h_state.reserve(sizeof(PsState))) return -1;
-        char *sp = (char *)scratch.p;
-        unsigned long long *mask_m = (unsigned long long *)sp, *mask_d = (unsigned long long *)(sp + o_md);
-        int *tile_m = (int *)(sp + o_tm), *tile_d = (int *)(sp + o_td);
-        PsFrame *frames = (PsFrame *)(sp + o_fr);
-        const PsState *si = (const PsState *)state.p + cur;
-        PsState *so = (PsState *)state.p + (cur ^ 1);
-        const float *hi = (const float *)hist.p + (size_t)cur * (size_t)p.B;
-        float *ho = (float *)hist.p + (size_t)(cur ^ 1) * (size_t)p.B;
+        const PsScratch sc(nt, max_frames);
+        if (scratch.reserve(sc.total)) return -1;
+        unsigned long long *mask_m = sc.mask_m.in(scratch), *mask_d = sc.mask_d.in(scratch);
+        int *tile_m = sc.tile_m.in(scratch), *tile_d = sc.tile_d.in(scratch);
+        PsFrame *frames = sc.frames.in(scratch);
+        const PsState *si = st.in();
+        PsState *so = st.out();
+        const float *hi = (const float *)hist.p + (size_t)st.cur * (size_t)p.B;
+        float *ho = (float *)hist.p + (size_t)(st.cur ^ 1) * (size_t)p.B;
         const float *x = (const float *)in_dev;
         hipLaunchKernelGGL(ps_match_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, hi, n, p, (const uint32_t *)pre.p, mask_m, mask_d, tile_m, tile_d);
         LR_LAUNCH_CHECK();
@@ -63,11 +57,9 @@ struct PsStage : lrhip_stage {
         hipLaunchKernelGGL(ps_emit_kernel, dim3((unsigned)grid), dim3(64), 0, ctx().stream, x, hi, ho, n, p, (const PsState *)so, (const PsFrame *)frames,
                            (float *)out_dev, cap);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        // the data-dependent count: the one small read-back of this stage
-        LR_HIP(hipMemcpyAsync(h_state.p, so, sizeof(PsState), hipMemcpyDeviceToHost, ctx().stream));
-        LR_HIP(hipStreamSynchronize(ctx().stream));
-        const PsState got = *(const PsState *)h_state.p;
+        st.flip();
+        PsState got;
+        if (st.fetch(got)) return -1;
         if (got.overflow || got.count > bound) return set_error("preamblesampler: %llu outputs in %llu frames exceed the bound %lu (%lu frames)", got.count, got.frames, bound, max_frames);
         return (long)got.count;
     }
@@ -127,18 +119,11 @@ static lrhip_stage_t *preamblesampler_create(const char *op)
 // =====================================================================================================
 struct MdStage : lrhip_stage {
     int invert = 0;
-    DeviceBuf state, scratch;                // state: two MdState (ping-pong)
-    PinnedBuf h_count;
-    int cur = 0;
+    DeviceBuf scratch;
+    Carried<MdState> st;                     // nothing pending, manchesterdecoder.lua:27
     const char *kind() const override { return "manchesterdecoder"; }
     long memory() const override { return -1; }
-    int reset() override
-    {
-        cur = 0;
-        MdState s[2];
-        memset(s, 0, sizeof(s));                             // nothing pending, manchesterdecoder.lua:27
-        return upload(state, s, sizeof(s));
-    }
+    int reset() override { return st.reset(); }
     // an output consumes two inputs of its own (the pending bit and the one that completes the pair); the first may be carried: (n + 1) / 2
     unsigned long max_output(unsigned long n) const override { return (n + 1) / 2; }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
@@ -147,14 +132,13 @@ struct MdStage : lrhip_stage {
         const unsigned long bound = max_output(n);
         if (cap < bound) return set_error("manchesterdecoder: output capacity %lu < bound %lu", cap, bound);
         const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
-        const size_t o_st = nt * sizeof(MSum), o_off = (o_st + nt * 4 + 7) / 8 * 8, total = o_off + nt * 8;
-        if (scratch.reserve(total) || h_count.reserve(sizeof(unsigned long long))) return -1;
-        char *sp = (char *)scratch.p;
-        MSum *tiles = (MSum *)sp;
-        int *t_state = (int *)(sp + o_st);
-        unsigned long long *t_off = (unsigned long long *)(sp + o_off);
-        const MdState *si = (const MdState *)state.p + cur;
-        MdState *so = (MdState *)state.p + (cur ^ 1);
+        const MdScratch sc(nt);
+        if (scratch.reserve(sc.total)) return -1;
+        MSum *tiles = sc.tiles.in(scratch);
+        int *t_state = sc.t_state.in(scratch);
+        unsigned long long *t_off = sc.t_off.in(scratch);
+        const MdState *si = st.in();
+        MdState *so = st.out();
         const uint8_t *x = (const uint8_t *)in_dev;
         hipLaunchKernelGGL(md_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, tiles);
         LR_LAUNCH_CHECK();
@@ -163,12 +147,11 @@ struct MdStage : lrhip_stage {
         hipLaunchKernelGGL(md_final_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, invert, (uint8_t *)out_dev, cap, (const int *)t_state,
                            (const unsigned long long *)t_off);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        LR_HIP(hipMemcpyAsync(h_count.p, &so->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx().stream));
-        LR_HIP(hipStreamSynchronize(ctx().stream));
-        const unsigned long long got = *(const unsigned long long *)h_count.p;
-        if (got > bound) return set_error("manchesterdecoder: %llu outputs exceed the bound %lu", got, bound);
-        return (long)got;
+        st.flip();
+        MdState got;
+        if (st.fetch(got)) return -1;
+        if (got.count > bound) return set_error("manchesterdecoder: %llu outputs exceed the bound %lu", got.count, bound);
+        return (long)got.count;
     }
 };
 

@@ -105,6 +105,24 @@ def test_preamblesampler_random_small_vs_literal_loop():
     assert_chunks_equal(sampler(T, pre, N), em.PreambleSamplerLiteral(T, pre, N), x, edges)
 
 
+def test_preamblesampler_three_tiles_and_an_event_on_the_last_sample():
+    """n = 2 * 1024 + 1: three tiles of the match pass, an odd count, where the two 4-byte lists of tile summaries need padding in front of
+    the frame list of the scratch; the third tile holds the last sample alone, and the last frame's j* falls on it"""
+    T, N, n = 3, 20, 2 * 1024 + 1
+    pre = np.array([0, 1, 1, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 1], np.uint8)
+    rng = np.random.default_rng(333)
+    x = es.alphabet_signal(n, 334)
+    es.plant_frame(x, 100, T, pre, N, rng)               # a frame in the first tile
+    es.plant_frame(x, n - 65, T, pre, N, rng)            # B = 64: the window lags behind the input, this frame's j* is sample n - 1
+    scout = em.PreambleSamplerFast(T, pre, N)
+    scout.process(x)
+    assert len(scout.frames) == 2 and scout.frames[0][1] < 1024 and scout.frames[1][1] == n - 1
+    blk = sampler(T, pre, N)
+    assert_chunks_equal(blk, em.PreambleSamplerLiteral(T, pre, N), x, [0, n])
+    blk.reset()
+    assert_chunks_equal(blk, em.PreambleSamplerLiteral(T, pre, N), x, [0, n - 30, n])
+
+
 def test_preamblesampler_long_quiet_stretches():
     T, N = 3, 5
     pre = np.array([0, 1, 1, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 1], np.uint8)
@@ -200,6 +218,18 @@ def test_manchesterdecoder_random(n, invert):
     blk = make(lr.ManchesterDecoderBlock, [invert], [types.Bit])
     assert blk.max_output(1001) == 501
     assert_chunks_equal(blk, em.ManchesterFast(invert), x, edges, bound=blk.max_output)
+
+
+@pytest.mark.parametrize("invert", [False, True])
+def test_manchesterdecoder_odd_length_vs_literal_loop(invert):
+    """n = 2 * 1024 + 1 against the literal loop, whole and cut once inside the last pair, into the same block after reset()"""
+    n = 2 * 1024 + 1
+    x = manchester_input(n, 333 + invert, 10)
+    blk = make(lr.ManchesterDecoderBlock, [invert], [types.Bit])
+    assert len(em.ManchesterLiteral(invert).process(x)) >= 2
+    assert_chunks_equal(blk, em.ManchesterLiteral(invert), x, [0, n])
+    blk.reset()
+    assert_chunks_equal(blk, em.ManchesterLiteral(invert), x, [0, n - 2, n])
 
 
 def test_manchesterdecoder_degenerate_inputs_and_one_sample_calls():

@@ -160,6 +160,25 @@ def test_frame_at_every_offset_before_a_tile_and_a_call_boundary(name):
 
 
 @pytest.mark.parametrize("name", NAMES)
+def test_three_tiles_and_a_frame_that_ends_on_the_last_bit(name):
+    """2 TILE + 1 + (L - 1) bits (L - 1: the most the stage carries): three tiles of window starts in the stream itself, the last one holding
+    a single position in front of the carried length.  The stage sizes its lists for a full carry on top, which makes 3 tiles for SCM and
+    SCM+ - an odd count, where the 4-byte list of tile summaries needs padding in front of the 64-bit lists of the scratch - and 4 for IDM."""
+    P = M.PROTOCOLS[name]
+    n = 2 * TILE + 1 + (P.L - 1)
+    rng = np.random.default_rng(333)
+    x = rng.integers(0, 2, n).astype(np.uint8)
+    x[50:50 + P.L] = M.random_frame(P, rng)[0]
+    x[n - P.L:] = M.random_frame(P, rng)[0]
+    want = literal(name, x)
+    assert len(want) >= 2
+    blk = framer(name)
+    assert same(run(blk, x), want)
+    blk.reset()
+    assert same(cut_run(blk, x, [0, n - P.L // 2, n], P.dtype), want)
+
+
+@pytest.mark.parametrize("name", NAMES)
 def test_overlapping_valid_windows(name):
     P = M.PROTOCOLS[name]
     rng = np.random.default_rng(21)

@@ -223,6 +223,33 @@ def test_frame_at_every_offset_before_a_tile_and_a_call_boundary(name):
         assert M.same_records(literal(name, xx), want)
 
 
+# ---- three tiles, the last frame ends on the last bit
+@pytest.mark.parametrize("name", NAMES)
+def test_three_tiles_and_a_frame_that_ends_on_the_last_bit(name):
+    """2 TILE + 1 + (the most the stage carries: 3192 bytes for AX.25, 543 for POCSAG) bits: three tiles of positions in the stream itself, the
+    last one holding a single position in front of the carried length.  The stages size their lists for a full carry on top, which makes 9 tiles
+    for AX.25 - an odd count, where the 4-byte list of tile summaries needs padding in front of the 64-bit lists of the scratch - and 4 for POCSAG."""
+    M = MODELS[name]
+    rng = np.random.default_rng(333)
+    if name == "ax25":
+        n = 2 * TILE + 1 + A.RAW_MAXLEN + 1 + 7
+        first, last = A.framed(MINIMAL), A.framed(A.random_octets(rng, naddr=2, payload_len=4))
+    else:
+        n = 2 * TILE + 1 + 543
+        first = P.transmission([(0x1a2b3 * 8 + 1, 3, [0x12345, 0xabcde]), (0x0f0f0 * 8 + 4, 0, [7])], nbatches=1)[0]
+        last = P.transmission([(0x0c0de * 8 + 2, 1, [1, 2, 3]), (0x15555 * 8 + 5, 2, [])], nbatches=1)[0]
+        assert len(first) == len(last) == 544
+    x = noise(rng, n)
+    x[60:60 + len(first)] = first
+    x[n - len(last):] = last
+    want = literal(name, x)
+    assert len(want) >= 2
+    blk = framer(name)
+    assert M.same_records(run(blk, x), want)
+    blk.reset()
+    assert M.same_records(cut_run(name, blk, x, [0, n - len(last) // 2, n]), want)
+
+
 # ---- AX.25 cases
 def ax_cuts(x):
     n = len(x)

@@ -102,6 +102,21 @@ def test_frame_at_every_offset_before_a_tile_and_a_call_boundary():
         assert same(cut_run(blk, y, [0, 350, 700]), want), off
 
 
+def test_three_tiles_and_a_frame_that_ends_on_the_last_bit():
+    """2 TILE + 1 + 103 bits (103: the most the stage carries): the match pass runs exactly three tiles, an odd count, where the 4-byte list of
+    tile summaries needs padding in front of the 64-bit lists of the scratch"""
+    n = 2 * TILE + 1 + (M.FRAME_LEN - 1)
+    x = np.random.default_rng(333).integers(0, 2, n).astype(np.uint8)
+    x[100:100 + M.FRAME_LEN] = M.encode_frame([0x1111, 0x2222, 0x3333, 0x4444])
+    x[n - M.FRAME_LEN:] = M.encode_frame([0xaaaa, 0x5555, 0x0f0f, 0xf0f0])
+    want = M.RDSFramerLiteral().process(x)
+    assert len(want) >= 2
+    blk = framer()
+    assert same(blk.process(x), want)
+    blk.reset()
+    assert same(cut_run(blk, x, [0, n - 40, n]), want)
+
+
 def _break_first(x, d):
     for i in range(min(d, M.BLOCK_LEN)):
         for j in range(i + 1, min(d, M.BLOCK_LEN)):

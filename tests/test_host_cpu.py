@@ -313,3 +313,19 @@ def test_fir_kernel_form_table_on_the_cpu(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
+def test_counted_stage_scratch_layouts_on_the_cpu(tmp_path):
+    """The stages with a data-dependent output count carve one scratch buffer into typed lists (luaradio_amd/csrc/stage_counted.h).  A wrong offset
+    or a missed alignment shows only at a tile count where the padding matters, so tools/host_carve_check.hip walks the layouts the stages use
+    - the same structs - over tile counts 1, 2, 3, 255, 256, 257 and frame bounds 1, 2 and an odd large one: in order, disjoint, aligned, covered."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "host_carve_check")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"),
+                        "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "host_carve_check.hip")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
