@@ -165,6 +165,20 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *   "manchesterdecoder:invert=0|1"                     (manchesterdecoder.lua:31-61) Bit -> Bit (input bytes read as & 1): a 0,1 pair gives 0 ^ invert, a
  *                                                      1,0 pair 1 ^ invert, an equal pair is a clock slip and the newer bit stays pending; count
  *                                                      data-dependent (<= (n + 1) / 2).
+ *   "varicodedecoder"                                  (varicodedecoder.lua:61-87; no parameters, any is refused) Bit -> Byte (one uint8_t per
+ *                                                      character): every byte joins a state; when the state's last two bytes both equal 0 the L - 2
+ *                                                      bytes in front of them (L = the state's length, 2 .. 11) are read as a number, most significant
+ *                                                      first, and its character in the PSK31 Varicode alphabet, if it has one, is emitted; the state is
+ *                                                      emptied there, and also once it holds more than 10 bytes.  Bytes are read as the reference reads
+ *                                                      them: a byte is a delimiter zero only when it equals 0 and a one only when it equals 1, so 2 or
+ *                                                      255 breaks a delimiter and counts as a 0 in the number.  As in the reference the 40 codes of 10
+ *                                                      bits (`Z`, `?`, ...) are never decoded: the state is emptied at length 11, in front of their
+ *                                                      second delimiter zero, and the first one stays behind in the new state, which costs the next
+ *                                                      character a bit of room - a 9-bit code right behind a lost character is lost too ("!Zx" gives
+ *                                                      "!x").  Count data-dependent (<= min(n, (n + 10) / 3): a character owns a code bit and 00, its
+ *                                                      second zero lies in the call, at most 10 bytes are carried in); the carried state is the state's
+ *                                                      length (0 .. 10) and its raw bytes; reset empties it; bit-identical however the stream is cut.
+ *                                                      Fuses with nothing.
  *   "rdsframer"                                        (rdsframer.lua:95-201; no parameters, any is refused) Bit -> 8-byte records
  *                                                      {uint16_t blocks[4]}, little-endian: the data words A, B, C, D of every 104-bit window whose four
  *                                                      26-bit blocks have a zero or single-bit-error syndrome under the offset words A, B, C (C' only
@@ -256,7 +270,7 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
- * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time
+ * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time
  * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */

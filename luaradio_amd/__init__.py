@@ -17,7 +17,7 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      FMPreemphasisFilterBlock, FloatToComplexBlock, ComplexToFloatBlock, FrequencyModulatorBlock,
                      PulseMatchedFilterBlock, ManchesterMatchedFilterBlock, AGCBlock, PowerSquelchBlock,
                      ZeroCrossingClockRecoveryBlock, SamplerBlock, SlicerBlock, DifferentialDecoderBlock, ClockSamplerBlock,
-                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock, RDSFramerBlock,
+                     BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock, VaricodeDecoderBlock, RDSFramerBlock,
                      SCMFramerBlock, SCMPlusFramerBlock, IDMFramerBlock, AX25FramerBlock, POCSAGFramerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock)
 from .sources import IQFileSource, RealFileSource, IQFileSink, RealFileSink  # noqa: F401

@@ -896,6 +896,26 @@ class ManchesterDecoderBlock(Block):
         return self._execute(x, np.uint8)
 
 
+class VaricodeDecoderBlock(Block):
+    """radio/blocks/protocol/varicodedecoder.lua. VaricodeDecoderBlock(): Bit -> Byte, the characters of a PSK31 bit stream: the bits in front of
+    every 00 are looked up in the Varicode alphabet, and a state of more than 10 bits is dropped.  As in the reference the codes of 10 bits
+    (`Z`, `?` and 38 more) are therefore never decoded, and a 9-bit code right behind one is lost with it.  The output count depends on the
+    data and not on how the stream is cut into calls; process(x) returns a uint8 array, so bytes(y) is the text."""
+    name = "VaricodeDecoderBlock"
+
+    def instantiate(self):
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.Byte)])
+
+    def op(self):
+        return "varicodedecoder"
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip varicodedecoder object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
 class RDSFramerBlock(Block):
     """radio/blocks/protocol/rdsframer.lua. RDSFramerBlock(): Bit -> RDSFrameType, one record of four 16-bit data words per 104-bit window whose
     four blocks check (single-bit errors corrected); after a frame the search resumes behind it.  The output count depends on the data;

@@ -536,8 +536,9 @@ def rds_receiver(rate=1102500.0, tune_offset=-250e3, framer=True):
 
 # ---- digital receivers.  By default they end at the bit stream; every Bit -> frame framer of the reference has a device form: RDSFramerBlock
 # (rds_receiver), SCMFramerBlock, SCMPlusFramerBlock and IDMFramerBlock (ert_receiver with framers=True), AX25FramerBlock and POCSAGFramerBlock
-# (ax25_receiver and pocsag_receiver with framer=True).  The decoders behind them (POCSAGDecoderBlock, RDSDecoderBlock, VaricodeDecoderBlock)
-# stay in the reference.
+# (ax25_receiver and pocsag_receiver with framer=True).  PSK31 has no framer: VaricodeDecoderBlock (Bit -> Byte) stands behind its bits, and
+# bpsk31_receiver with decoder=True ends in it.  The decoders that turn frames into objects and strings on the host (POCSAGDecoderBlock,
+# RDSDecoderBlock) stay in the reference.
 def ax25_receiver(rate=1e6, tune_offset=-100e3, framer=False):
     """The compute blocks of examples/rtlsdr_ax25.lua:14-24 as one device chain, by default up to the Bit stream AX25FramerBlock reads:
     Tuner(offset, 12e3, 80) -> NBFMDemodulator(3e3, 3e3) -> Hilbert(129) -> Translator(-1700) -> Lowpass(128, 750) -> Discriminator(1.25)
@@ -579,15 +580,19 @@ def pocsag_receiver(rate=1e6, tune_offset=-100e3, baudrate=1200, framer=False):
     return g.initialize()
 
 
-def bpsk31_receiver(rate):
-    """The compute blocks of radio/composites/bpsk31receiver.lua:20-44 as one device chain, up to the Bit stream VaricodeDecoderBlock reads:
+def bpsk31_receiver(rate, decoder=False):
+    """The compute blocks of radio/composites/bpsk31receiver.lua:20-44 as one device chain, by default up to the Bit stream VaricodeDecoderBlock reads:
     Lowpass(128, 100) -> RootRaisedCosine(101, 1, 31.25) -> BinaryPhaseCorrector(50) -> ComplexToReal -> ClockSampler(31.25) -> Slicer ->
     DifferentialDecoder(true).  The reference samples the complex corrected signal at the clock recovered from its real part and then takes
     the real part (:36-40): the same as sampling the real part, so the chain is linear.  The corrector and ComplexToReal run as one stage, and
-    the slicer and the decoder in the clock sampler's final pass."""
+    the slicer and the decoder in the clock sampler's final pass.  With decoder=True the chain ends in VaricodeDecoderBlock (:36, :42) and returns
+    types.Byte, the characters: bytes(y) is the text."""
     baudrate = 31.25
-    return _receiver([B.LowpassFilterBlock(128, 100), B.RootRaisedCosineFilterBlock(101, 1, baudrate), B.BinaryPhaseCorrectorBlock(50),
-                      B.ComplexToRealBlock(), B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)], rate)
+    blocks = [B.LowpassFilterBlock(128, 100), B.RootRaisedCosineFilterBlock(101, 1, baudrate), B.BinaryPhaseCorrectorBlock(50),
+              B.ComplexToRealBlock(), B.ClockSamplerBlock(baudrate), B.SlicerBlock(), B.DifferentialDecoderBlock(True)]
+    if decoder:
+        blocks.append(B.VaricodeDecoderBlock())
+    return _receiver(blocks, rate)
 
 
 # The preambles and frame lengths (in bits) of the three ERT protocols, as their framers define them

@@ -28,6 +28,7 @@
 #include "kernels_digital.h"
 #include "kernels_bitscan.h"
 #include "kernels_preamble.h"
+#include "kernels_varicode.h"
 #include "kernels_rdsframer.h"
 #include "kernels_ertframer.h"
 #include "kernels_ax25framer.h"
@@ -421,6 +422,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "idmframer") return plain_create<EfStage<EF_IDM>>(op, EfProto<EF_IDM>::REC);
         if (head == "ax25framer") return plain_create<AxStage>(op, AX_REC);
         if (head == "pocsagframer") return plain_create<PgStage>(op, PG_REC);
+        // nor does the Varicode decoder (stage_preamble.h)
+        if (head == "varicodedecoder") return plain_create<VcStage>(op, 1);
         if (head == "manchesterdecoder") {
             if (!parse_op(op, name, kv, {"invert"})) return nullptr;
             return manchesterdecoder_create(kv, op);

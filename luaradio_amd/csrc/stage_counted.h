@@ -1,5 +1,5 @@
 // stage_counted.h - the host pieces shared by the stages whose output count depends on the data (the sampler and clocksampler of stage_digital.h,
-// the preamble sampler and Manchester decoder of stage_preamble.h, the five framers of stage_framers.h): the state and the bytes carried between
+// the preamble sampler, Manchester decoder and Varicode decoder of stage_preamble.h, the five framers of stage_framers.h): the state and the bytes carried between
 // calls, the one count read-back per call, the carve-up of a call's scratch, and the constructor of a stage without parameters.
 // (part of liblrhip.so; included by lrhip.hip after stage.h, one translation unit.  Plain host code: tools/host_carve_check.hip checks the
 // scratch layouts on the CPU)
@@ -56,7 +56,7 @@ struct Carve {
     }
 };
 
-// The eight layouts (members are taken in the order they are declared).  nt = tiles of the call.
+// The nine layouts (members are taken in the order they are declared).  nt = tiles of the call.
 struct RfScratch : Carve {
     Region<unsigned long long> mask_v; Region<int> tile_v; Region<long long> starts;
     RfScratch(unsigned long nt, unsigned long bound)
@@ -94,6 +94,13 @@ struct ZcScratch : Carve {
     explicit ZcScratch(unsigned long nt)
         : tiles(take<HSum>(nt)), t_h(take<int>(2 * (size_t)nt)), t_rpos(take<long long>(nt)), t_kind(take<int>(2 * (size_t)nt)), t_o(take<double>(nt)),
           t_prev(take<int>(2 * (size_t)nt)), t_cnt(take<unsigned>(2 * (size_t)nt)), t_bit(take<int>(2 * (size_t)nt)) {}
+};
+// tile maps, tile offsets, tile entry states, tile counts, then per thread "entry state, offset in the tile"
+struct VcScratch : Carve {
+    Region<VcMap> tiles; Region<unsigned long long> t_off; Region<int> t_state; Region<unsigned> t_cnt, t_thread;
+    explicit VcScratch(unsigned long nt)
+        : tiles(take<VcMap>(nt)), t_off(take<unsigned long long>(nt)), t_state(take<int>(nt)), t_cnt(take<unsigned>(nt)),
+          t_thread(take<unsigned>((size_t)nt * 256)) {}
 };
 struct SamplerScratch : Carve {
     Region<SSum> tiles; Region<int> t_h; Region<unsigned long long> t_off;                 // (t_h in slots of 8 bytes per tile)

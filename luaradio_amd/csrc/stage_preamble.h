@@ -1,6 +1,7 @@
-// stage_preamble.h - PreambleSamplerBlock and ManchesterDecoderBlock (kernels_preamble.h), created through lrhip_unary_create
-// ("preamblesampler:period=T:num_samples=N:preamble=0101..." and "manchesterdecoder:invert=0|1").  Both have a data-dependent output count:
-// run() returns the exact count, read back from the device after the last pass (one small synchronous copy per call), and memory() = -1.
+// stage_preamble.h - PreambleSamplerBlock and ManchesterDecoderBlock (kernels_preamble.h) and VaricodeDecoderBlock (kernels_varicode.h), created
+// through lrhip_unary_create ("preamblesampler:period=T:num_samples=N:preamble=0101...", "manchesterdecoder:invert=0|1" and "varicodedecoder").
+// All three have a data-dependent output count: run() returns the exact count, read back from the device after the last pass (one small
+// synchronous copy per call), and memory() = -1.
 // (part of liblrhip.so; included by lrhip.hip after stage_digital.h, one translation unit)
 #pragma once
 
@@ -168,3 +169,48 @@ static lrhip_stage_t *manchesterdecoder_create(const std::map<std::string, doubl
     if (q->reset()) return nullptr;
     return q.release();
 }
+
+// =====================================================================================================
+// VaricodeDecoderBlock: Bit -> Byte, data-dependent count (the Manchester decoder's shape: tile summaries of state maps, one carry workgroup,
+// a final pass that stores packed - with the characters counted from the true entry states in between, kernels_varicode.h)
+// =====================================================================================================
+struct VcStage : lrhip_stage {
+    DeviceBuf scratch;
+    Carried<VcState, VC_MAX_LEN> st;         // an empty state, varicodedecoder.lua:22
+    const char *kind() const override { return "varicodedecoder"; }
+    long memory() const override { return -1; }
+    int reset() override { return st.reset(); }
+    unsigned long max_output(unsigned long n) const override { return vc_max_output(n); }
+    long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
+    {
+        if (!n) return 0;
+        const unsigned long bound = max_output(n);
+        if (cap < bound) return set_error("varicodedecoder: output capacity %lu < bound %lu", cap, bound);
+        const unsigned long nt = (n + DG_TILE - 1) / DG_TILE;
+        const VcScratch sc(nt);
+        if (scratch.reserve(sc.total)) return -1;
+        VcMap *tiles = sc.tiles.in(scratch);
+        unsigned long long *t_off = sc.t_off.in(scratch);
+        int *t_state = sc.t_state.in(scratch);
+        unsigned *t_cnt = sc.t_cnt.in(scratch), *t_thread = sc.t_thread.in(scratch);
+        const VcState *si = st.in();
+        VcState *so = st.out();
+        const uint8_t *ci = st.ci(), *x = (const uint8_t *)in_dev;
+        hipLaunchKernelGGL(vc_summary_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, tiles);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vc_carry_kernel, dim3(1), dim3(256), 0, ctx().stream, (const VcMap *)tiles, nt, x, n, si, ci, so, st.co(), t_state);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vc_count_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, si, ci, (const int *)t_state, t_cnt, t_thread);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vc_offsets_kernel, dim3(1), dim3(256), 0, ctx().stream, (const unsigned *)t_cnt, nt, t_off, so);
+        LR_LAUNCH_CHECK();
+        hipLaunchKernelGGL(vc_final_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, n, si, ci, (const unsigned *)t_thread,
+                           (const unsigned long long *)t_off, (uint8_t *)out_dev, cap);
+        LR_LAUNCH_CHECK();
+        st.flip();
+        VcState got;
+        if (st.fetch(got)) return -1;
+        if (got.count > bound) return set_error("varicodedecoder: %llu outputs exceed the bound %lu", got.count, bound);
+        return (long)got.count;
+    }
+};

@@ -1,7 +1,7 @@
 """Sample types - mirrors radio/types/complexfloat32.lua:19-24 and radio/types/float32.lua:17-21.
 
 ComplexFloat32 = struct{float real, imag} (8 B interleaved) == numpy complex64;
-Float32 = struct{float value} (4 B) == numpy float32; Bit = struct{uint8_t value} (1 B) == numpy uint8; RDSFrameType = struct{uint16_t blocks[4]} (8 B) == a
+Float32 = struct{float value} (4 B) == numpy float32; Bit = struct{uint8_t value} (1 B) and Byte = struct{uint8_t value} (1 B) == numpy uint8; RDSFrameType = struct{uint16_t blocks[4]} (8 B) == a
 row of four numpy uint16; SCMFrameType (16 B), SCMPlusFrameType (16 B) and IDMFrameType (88 B), AX25FrameType (416 B) and POCSAGFrameType (256 B) == numpy structured
 dtypes of the records in include/lrhip.h.  Vectors are contiguous numpy arrays, which is the
 same raw layout the reference writes on its pipes (radio/types/cstruct.lua:87-126).
@@ -34,6 +34,8 @@ ComplexFloat32 = _SampleType("ComplexFloat32", np.complex64, 8)
 Float32 = _SampleType("Float32", np.float32, 4)
 # radio/types/bit.lua: struct bit {uint8_t value} (1 B)
 Bit = _SampleType("Bit", np.uint8, 1)
+# radio/types/byte.lua: struct byte {uint8_t value} (1 B); the same raw layout as Bit, so type_of(uint8) keeps answering Bit
+Byte = _SampleType("Byte", np.uint8, 1)
 # radio/blocks/protocol/rdsframer.lua:71-75: rds_frame_t {uint16_t blocks[4]} (8 B); a vector of n frames is an (n, 4) uint16 array
 RDSFrameType = _SampleType("RDSFrameType", np.dtype((np.uint16, (4,))), 8)
 

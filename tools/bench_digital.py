@@ -4,8 +4,8 @@ decoder chain and the clock recovery alone, on resident Float32 samples; the bin
 ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the three digital receivers up to their bit streams.  HIP-event timing on the launch stream after warm-up, as
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
 (4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
-PAM / QAM modulators, of the SCM / SCM+ / IDM framers and of the AX.25 / POCSAG framers instead (modulator_rows, ert_framer_rows,
-packet_framer_rows)."""
+PAM / QAM modulators, of the SCM / SCM+ / IDM framers, of the AX.25 / POCSAG framers and of the Varicode decoder instead (modulator_rows,
+ert_framer_rows, packet_framer_rows, varicode_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -24,7 +24,8 @@ def main():
     ap.add_argument("--modulators", action="store_true", help="only the PAM / QAM modulator rows (profiles/modulator_table.jsonl)")
     ap.add_argument("--ert-framers", action="store_true", help="only the SCM / SCM+ / IDM framer rows (profiles/ert_framer_table.jsonl)")
     ap.add_argument("--packet-framers", action="store_true", help="only the AX.25 / POCSAG framer rows (profiles/packet_framer_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --ert-framers / --packet-framers: append the rows to this file as well")
+    ap.add_argument("--varicode", action="store_true", help="only the Varicode decoder rows (profiles/varicode_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --ert-framers / --packet-framers / --varicode: append the rows to this file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
@@ -32,6 +33,8 @@ def main():
         return ert_framer_rows(args)
     if args.packet_framers:
         return packet_framer_rows(args)
+    if args.varicode:
+        return varicode_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -295,6 +298,63 @@ def packet_framer_rows(args):
             if args.out:
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
+
+
+def varicode_rows(args):
+    """VaricodeDecoderBlock (kernels_varicode.h) on 2^log2-samples resident Bit bytes (--log2-samples 24 for the recorded rows), two inputs:
+    random bits, and an encoded text (random characters with codes of at most 8 bits, the encoder of tests/helpers/varicode_model.py, tiled) -
+    each next to a read-only pass over the same bytes (torch's sum), the two alternating three times.  A call includes the decoder's one count
+    read-back.  A record, not an acceptance criterion: 31.25 bit/s is no hot path.  --out appends the rows to a file
+    (profiles/varicode_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+    from tests.helpers import varicode_model as V
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+    n = 1 << args.log2_samples
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    short = [c for c in range(128) if V.CODE[c] < 0x100]
+    text = V.encode(rng.choice(short, 1 << 14).tolist())
+    for kind in ("random", "text"):
+        bits = rng.integers(0, 2, n).astype(np.uint8) if kind == "random" else np.tile(text, -(-n // len(text)))[:n]
+        x = torch.from_numpy(bits).cuda()
+        blk = lr.VaricodeDecoderBlock()
+        blk.rate = 31.25
+        blk.differentiate([types.Bit])
+        blk.initialize()
+        cap = blk.max_output(n)
+        y = torch.empty(cap + 64, dtype=torch.uint8, device="cuda")
+        count = []
+
+        def call():                                   # successive calls continue one stream (the carried state of the call before)
+            count.append(blk.process_device(x.data_ptr(), n, y.data_ptr(), cap))
+        ms, ms_read = [], []
+        for _ in range(3):
+            ms.append(timed(call))
+            ms_read.append(timed(lambda: x.sum()))
+        row = {"row": "VaricodeDecoderBlock %s" % kind, "bits": n, "characters": int(count[-1]), "ms": ms, "read_only_ms": ms_read,
+               "share_of_read_only": round(min(ms_read) / min(ms), 3), "Gbit/s": round(n / min(ms) / 1e6, 2)}
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":

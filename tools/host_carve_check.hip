@@ -1,4 +1,4 @@
-// host_carve_check.hip - the scratch layouts of the eight counted stages (luaradio_amd/csrc/stage_counted.h: the structs the stages' run()
+// host_carve_check.hip - the scratch layouts of the nine counted stages (luaradio_amd/csrc/stage_counted.h: the structs the stages' run()
 // use, not copies), on the CPU: for tile counts around 1 and 256 and frame bounds 1, 2 and an odd large value, the regions lie in the order
 // they were taken and do not overlap, each starts on a multiple of its alignment, and the total covers them all.
 //   hipcc --offload-arch=gfx950 -O1 -std=c++17 -I luaradio_amd/csrc -I include -o /tmp/host_carve_check tools/host_carve_check.hip && /tmp/host_carve_check
@@ -10,6 +10,7 @@
 #include "kernels_digital.h"
 #include "kernels_bitscan.h"
 #include "kernels_preamble.h"
+#include "kernels_varicode.h"
 using namespace lrhip;
 #include "stage.h"
 #include "stage_counted.h"
@@ -41,7 +42,7 @@ int main()
 {
     const unsigned long tiles[] = {1, 2, 3, 255, 256, 257}, bounds[] = {1, 2, 1000003};
     const size_t rf[] = {8, 4, 8, 0}, ef[] = {8, 8, 4, 8, 0}, ax[] = {8, 4, 8, 8, 1, 0}, pg[] = {8, 4, 0}, ps[] = {8, 8, 4, 4, 16, 0}, md[] = {8, 4, 8, 0},
-                 zc[] = {8, 4, 8, 4, 8, 4, 4, 4, 0}, sm[] = {8, 4, 8, 0};
+                 zc[] = {8, 4, 8, 4, 8, 4, 4, 4, 0}, sm[] = {8, 4, 8, 0}, vc[] = {8, 8, 4, 4, 4, 0};
     int cases = 0;
     for (unsigned long nt : tiles)
         for (unsigned long b : bounds) {
@@ -54,7 +55,8 @@ int main()
             check("manchesterdecoder", nt, b, MdScratch(nt), md);
             check("clocksampler", nt, b, ZcScratch(nt), zc);
             check("sampler", nt, b, SamplerScratch(nt), sm);
-            cases += 10;
+            check("varicodedecoder", nt, b, VcScratch(nt), vc);
+            cases += 11;
         }
     if (failures) {
         printf("%d of %d layouts FAILED\n", failures, cases);
