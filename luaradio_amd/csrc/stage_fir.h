@@ -770,6 +770,9 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             grid = (unsigned)((pr.ntiles + pr.run - 1) / pr.run);
         } else {
             pr.warm_waves = 4; pr.run = 1;
+            // pair mode without the recurrence (a 136-tap decimate-by-5 Float32 filter on its own): the kernel's prefetch loads from fix_edge / fix_prev
+            // unconditionally on every interior tile - readable dummies here as well (the taps: 136 floats), not the null pointers of the memset above
+            if (G::PAIR) { pr.fix_edge = pr.fix_prev = (const float2 *)d_taps.p; pr.fix_inv_gain = 1.0; }
             // ONESHOT: a workgroup per tile, handed out in address order (short filters are a streaming problem: common.h grid_for)
             grid = (unsigned)((ONESHOT || fir_knobs().win_oneshot || pr.ntiles < slots) ? pr.ntiles : slots);
         }

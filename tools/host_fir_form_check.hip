@@ -132,6 +132,32 @@ int main()
         {"/50, 5 889 taps", shp(5889, 2, 50, 0), DEF, true, F::DecimLds1, 1, true, true},
         {"direct: /50, 5 890 taps", shp(5890, 2, 50, 0), DEF, true, F::Direct, 1, false, false},
         {"D = 1 without a table: LDS-staged, but not for in-place input", shp(5000, 2, 1, 0), DEF, true, F::DecimLds1, 1, false, true},
+        // ---- the shapes of tests/test_gpu_bounds.py (test_fir_form, test_hilberttransform, test_chain): each case reaches the form it claims to
+        {"bounds: decfft", decf(shp(128, 2, 4, 48)), DEF, true, F::DecFft, 1, true, false},
+        {"bounds: decfft at an offset of 1 or 3 floats", decf(shp(128, 2, 4, 48)), DEF, false, F::Direct, 1, true, false},
+        {"bounds: winshort", shp(16, 2, 1, 8), DEF, true, F::WinShort, 1, true, false},
+        {"bounds: winshortc", ctaps(shp(16, 2, 1, 16), true), DEF, true, F::WinShortC, 1, true, false},
+        {"bounds: shortreal", shp(16, 1, 1, 9), DEF, true, F::ShortReal, 1, false, false},
+        {"bounds: winpair", shp(136, 1, 5, 54), DEF, true, F::WinPair, 1, true, false},
+        {"bounds: decimlds1", shp(128, 1, 50, 0), DEF, true, F::DecimLds1, 1, true, false},
+        {"bounds: decimlds2", shp(128, 2, 50, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"bounds: direct", shp(128, 2, 1, 36), DEF, false, F::Direct, 1, true, false},
+        {"bounds: mfmacc, 64 complex taps = 128 + 2 x 15 + 2 + 3 over 4 steps", ctaps(shp(64, 2, 1, 40)), DEF, true, F::MfmaCc, 1, true, false},
+        {"bounds: mfmacc at an offset of 1 or 3 floats", ctaps(shp(64, 2, 1, 40)), DEF, false, F::Direct, 1, true, false},
+        {"bounds: persistent-cf32", shp(128, 2, 1, 36), DEF, true, F::MfmaPersistent, 1, true, false},
+        {"bounds: persistent-f32", shp(128, 1, 1, 37), DEF, true, F::MfmaPersistent, 1, true, false},
+        {"bounds: persistent-cf32-d5", shp(128, 2, 5, 51), DEF, true, F::MfmaPersistent, 1, true, true},
+        {"bounds: persistent-cf32-d5 at an offset of 1 or 3 floats", shp(128, 2, 5, 51), DEF, false, F::Direct, 1, true, true},
+        {"bounds: generic-cf32", shp(124, 2, 1, 35), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"bounds: generic-cf32 at an offset of 1 or 3 floats", shp(124, 2, 1, 35), DEF, false, F::Direct, 1, true, false},
+        {"bounds: generic-f32", shp(132, 1, 1, 38), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"bounds: chain tuner", rot(shp(128, 2, 5, 51)), DEF, true, F::MfmaPersistent, 1, true, true},
+        {"bounds: chain tuner-discriminator", rel(post(rot(shp(128, 2, 5, 51)))), DEF, true, F::MfmaPersistent, 5120, true, false},
+        {"bounds: chain tuner-discriminator, exact", post(rot(shp(128, 2, 5, 51))), DEF, true, F::MfmaPersistent, 1, true, false},
+        {"bounds: chain filter-discriminator", rel(post(shp(128, 2, 1, 36))), DEF, true, F::MfmaPersistent, 1, true, false},
+        {"bounds: chain tuner50-magnitude", rot(shp(128, 2, 50, 0)), DEF, true, F::DecimLds2, 1, true, true},
+        {"bounds: chain tuner50-discriminator", rel(post(rot(shp(128, 2, 50, 0)))), DEF, true, F::DecimLds2, 1, true, false},
+        {"bounds: chain audio-tail", iir(shp(136, 1, 5, 54)), DEF, true, F::WinPair, 12800, true, false},
     };
     const FirShape c1276 = fft(1276, 2, 1280), r1276 = fft(1276, 1, 1280), r768 = fft(768, 1, 768), c2048 = fft(2048, 2, 0, 1);
     const std::vector<FftRow> fft_rows = {
@@ -189,6 +215,30 @@ int main()
         {"LRHIP_FFT_NO_4K, cf32 1 276", c1276, K([](FirKnobs &k) { k.fft_no_4k = true; }), 1L << 24, 256, X::Pols},
         {"LRHIP_FFT_NO_4K LRHIP_FFT_POLS=0, cf32 1 276", c1276, K([](FirKnobs &k) { k.fft_no_4k = true; k.fft_pols = 0; }), 1L << 24, 256, X::Pass1024},
         {"LRHIP_FFT_NO_4K, cf32 2 048", c2048, K([](FirKnobs &k) { k.fft_no_4k = true; }), 1L << 24, 256, X::Long64},
+        // ---- the shapes of tests/test_gpu_bounds.py (test_fir_fft_form: n_out = 3 T, the largest call of each case; every smaller call takes the same form)
+        {"bounds: cf32 128", fft(128, 2), DEF, 3L * 896, 256, X::Pass1024}, {"bounds: cf32 512", fft(512, 2), DEF, 3L * 512, 256, X::Pass1024},
+        {"bounds: cf32 513", fft(513, 2, 768), DEF, 3L * 3328, 256, X::Wg4k}, {"bounds: cf32 1 281", fft(1281, 2, 1280), DEF, 3L * 2816, 256, X::Wg4k},
+        {"bounds: cf32 1 282", fft(1282, 2, 0, 1), DEF, 3L * 2048, 256, X::Long64}, {"bounds: cf32 2 049", fft(2049, 2, 0, 1), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: cf32 2 050", fft(2050, 2, 0, 2), DEF, 3L * 2048, 256, X::Long64}, {"bounds: cf32 4 097", fft(4097, 2, 0, 2), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: cf32 4 098", fft(4098, 2, 0, 3), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: complex taps 128", ctaps(fft(128, 2)), DEF, 3L * 896, 256, X::Pass1024}, {"bounds: complex taps 512", ctaps(fft(512, 2)), DEF, 3L * 512, 256, X::Pass1024},
+        {"bounds: complex taps 513", ctaps(fft(513, 2, 768)), DEF, 3L * 3328, 256, X::Wg4k}, {"bounds: complex taps 1 281", ctaps(fft(1281, 2, 1280)), DEF, 3L * 2816, 256, X::Wg4k},
+        {"bounds: complex taps 1 282", ctaps(fft(1282, 2, 0, 1)), DEF, 3L * 2048, 256, X::Long64}, {"bounds: complex taps 2 049", ctaps(fft(2049, 2, 0, 1)), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: complex taps 2 050", ctaps(fft(2050, 2, 0, 2)), DEF, 3L * 2048, 256, X::Long64}, {"bounds: complex taps 4 097", ctaps(fft(4097, 2, 0, 2)), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: complex taps 4 098", ctaps(fft(4098, 2, 0, 3)), DEF, 3L * 2048, 256, X::Long64},
+        {"bounds: f32 128", fft(128, 1), DEF, 3L * 1792, 256, X::Pass1024}, {"bounds: f32 512", fft(512, 1), DEF, 3L * 1024, 256, X::Pass1024},
+        {"bounds: f32 513", fft(513, 1, 768), DEF, 3L * 6656, 256, X::Wave64}, {"bounds: f32 1 281", fft(1281, 1, 1280), DEF, 3L * 5632, 256, X::Wave64},
+        {"bounds: f32 1 282", fft(1282, 1, 0, 1), DEF, 3L * 4096, 256, X::Long64}, {"bounds: f32 2 049", fft(2049, 1, 0, 1), DEF, 3L * 4096, 256, X::Long64},
+        {"bounds: f32 2 050", fft(2050, 1, 0, 2), DEF, 3L * 4096, 256, X::Long64}, {"bounds: f32 4 097", fft(4097, 1, 0, 2), DEF, 3L * 4096, 256, X::Long64},
+        {"bounds: f32 4 098", fft(4098, 1, 0, 3), DEF, 3L * 4096, 256, X::Long64},
+        {"bounds: one-sample calls", fft(513, 2, 768), DEF, 1, 256, X::Wg4k}, {"bounds: one-sample calls, f32", fft(513, 1, 768), DEF, 1, 256, X::Wave64},
+        // test_fir_fft_large: the smallest launches that reach the wave-per-block form on a ComplexFloat32 stream and the partitioned form on a Float32 stream
+        {"bounds: large wave64, 5 120 blocks", fft(1281, 2, 1280), DEF, 5119L * 2816 + 1, 256, X::Wave64}, {"bounds: one sample less", fft(1281, 2, 1280), DEF, 5119L * 2816, 256, X::Wg4k},
+        {"bounds: large wave64, the call of 3 samples behind it", fft(1281, 2, 1280), DEF, 3, 256, X::Wg4k},
+        {"bounds: large pols, 2 049 transforms", fft(768, 1, 768), DEF, 4096L * 3328 + 1, 256, X::Pols}, {"bounds: one sample less, f32", fft(768, 1, 768), DEF, 4096L * 3328, 256, X::Wave64},
+        // test_chain: the merged cascade of three 256-tap filters, the discriminator in front of an overlap-save filter
+        {"bounds: chain fir-cascade, 766 taps", fft(766, 2, 768), DEF, 3L * 3328, 256, X::Wg4k},
+        {"bounds: chain discriminator-fir", pre(fft(128, 1)), DEF, 3L * 1792, 256, X::Pass1024},
     };
     // align() / direct_io_ok() of the overlap-save shapes: lcm of the partitions' block advances (x 2 on a Float32 stream); in place only in one launch
     const std::vector<Row> fft_shape_rows = {
@@ -202,6 +252,8 @@ int main()
         {"4 097 taps: two partitions, one launch", fft(4097, 2, 0, 2), DEF, true, F::OverlapSave, 1024, true, false},
         {"4 098 taps: the second launch re-reads y", fft(4098, 2, 0, 3), DEF, true, F::OverlapSave, 7680, false, false},
         {"cf32 1 276 taps from an unaligned chunk", c1276, DEF, false, F::OverlapSave, 1536, true, false},
+        {"bounds: chain fir-cascade, 766 taps = partitions of 512 and 254", fft(766, 2, 768), DEF, true, F::OverlapSave, 1536, true, false},
+        {"bounds: chain discriminator-fir", pre(fft(128, 1)), DEF, true, F::OverlapSave, 1792, false, false},
     };
     const FirKnobs v1 = K([](FirKnobs &k) { k.decim_v1 = true; }), no_lds = K([](FirKnobs &k) { k.no_disc_epi_lds = true; }),
                    no_other = K([](FirKnobs &k) { k.no_disc_epi_other_d = true; }), wc = K([](FirKnobs &k) { k.win_cplx = true; });
@@ -234,6 +286,7 @@ int main()
         {"unary: decfft", fir_can_post_unary(decf(shp(128, 2, 11, 0))), false}, {"unary: 5 890 taps", fir_can_post_unary(shp(5890, 2, 50, 0)), false},
         {"hilbert: 129 taps", fir_hilbert_ok(shp(129, 1, 1, 37)), true}, {"hilbert: no table", fir_hilbert_ok(shp(129, 1, 1, 0)), false},
         {"hilbert: overlap-save", fir_hilbert_ok(fft(129, 1)), false}, {"hilbert: cf32", fir_hilbert_ok(shp(129, 2, 1, 37)), false},
+        {"bounds: hilbert 33 taps", fir_hilbert_ok(shp(33, 1, 1, 13)), true}, {"bounds: hilbert 65 taps", fir_hilbert_ok(shp(65, 1, 1, 21)), true},
     };
 
     int bad = 0;
