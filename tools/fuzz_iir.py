@@ -1,5 +1,7 @@
-"""Fuzz (round 6, GPU box: python tools/fuzz_iir.py [seeds]): IIRFilterBlock with random stable filters - feedback orders 1 .. 8 (poles of radius 0.3 .. 0.97, real
-and in conjugate pairs), 1 .. 8 feed-forward taps, ComplexFloat32 / Float32 streams, random lengths (1 .. 1.5 M samples) and ragged chunk cuts - against the
+"""Fuzz (round 6, GPU box: python tools/fuzz_iir.py [seeds]): IIRFilterBlock with random stable filters - feedback orders 1 .. 8 (poles real and in conjugate
+pairs; their radii from one of three bands per filter, 0.3 .. 0.97, 0.97 .. 0.992 and 0.992 .. 0.9999, so that the one-shot, the whole-warm-up-tile and the
+three-pass forms are all drawn: tests/helpers/iir_forms.py has the rule), 1 .. 16 feed-forward taps, ComplexFloat32 / Float32 streams, random lengths (1 .. 2.2 M
+samples: a host call of that length is cut into pieces of more than 256 tiles, so the carry scan runs with two tiles per thread) and ragged chunk cuts - against the
 sequential double-precision recurrence (scipy.signal.lfilter on the same Float32 coefficients), relative to the output's scale.  The device evaluates the recurrence
 as a scan over affine maps (kernels_iir.h), so what is checked is the scan's algebra and its tile / chunk seams, relative to the output's scale: 2e-5, or 3 x what scipy's Float32 lfilter loses on the same filter (ill-conditioned draws)."""
 import os
@@ -20,17 +22,18 @@ def main():
         rng = np.random.default_rng(52000 + seed)
         order = int(rng.integers(1, 9))
         poles = []
+        lo, hi = [(0.3, 0.97), (0.97, 0.992), (0.992, 0.9999)][seed % 3]
         while len(poles) < order:
-            r = float(rng.uniform(0.3, 0.97))
+            r = float(rng.uniform(lo, hi))
             if order - len(poles) >= 2 and rng.integers(0, 2):
                 th = float(rng.uniform(0.05, 3.0))
                 poles += [r * np.exp(1j * th), r * np.exp(-1j * th)]
             else:
                 poles.append(r * (1 if rng.integers(0, 2) else -1))
         a = np.real(np.poly(poles)).astype(np.float32)
-        b = rng.uniform(-1, 1, int(rng.integers(1, 9))).astype(np.float32)
+        b = rng.uniform(-1, 1, int(rng.integers(1, 17))).astype(np.float32)
         cplx = bool(rng.integers(0, 2))
-        n = int(rng.integers(1, 1500000)) if seed % 3 else int(rng.integers(1, 5000))
+        n = int(rng.integers(1, 2200000)) if seed % 4 else int(rng.integers(1, 5000))
         x = (rng.uniform(-1, 1, n) + 1j * rng.uniform(-1, 1, n)).astype(np.complex64) if cplx else rng.uniform(-1, 1, n).astype(np.float32)
         cuts = sorted(int(v) for v in rng.integers(1, max(n, 2), int(rng.integers(0, 5)))) if n > 1 else []
         blk = lr.IIRFilterBlock(b, a)
