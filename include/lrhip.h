@@ -273,6 +273,36 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time
  * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
+
+/* Port tables: the many-ported stages.  Four ops of lrhip_unary_create (re / im / constant_complex / input_complex ignored) make stages
+ * with N input ports or N output ports; they are stateless, memory() = 0, and fuse with nothing:
+ *   "interleave:channels=N:size=4|8"      (interleave.lua:47-58) N inputs of 4- or 8-byte samples -> out[N i + k] = in_k[i]; bytes are moved,
+ *                                         never interpreted.  max_output(n) = N n; returns N n.
+ *   "deinterleave:channels=N:size=4|8"    (deinterleave.lua:49-63 with index = 0) one input -> out_j[i] = in[N i + j]: port j receives
+ *                                         ceil((n - j) / N) samples, n need be no multiple of N.  max_output(n) = ceil(n / N); returns port 0's
+ *                                         count.  The reference's carried index is the caller's: it rotates the table (entry j = the channel of
+ *                                         this call's j-th sample).
+ *   "wavpack:channels=N:bits=8|16|32"     (sinks/wavfile.lua:171-176) N Float32 inputs -> records of N raw samples (u8 / s16le / s32le),
+ *                                         raw[N i + k] = pack(in_k[i]) with the arithmetic and the saturation rule of lrhip_format_pack_create.
+ *                                         output_size = N bits / 8; returns n records.
+ *   "wavunpack:channels=N:bits=8|16|32"   (sources/wavfile.lua:235-239) n whole records (input_size = N bits / 8) -> N Float32 outputs,
+ *                                         out_k[i] = (raw[N i + k] - offset) / scale as lrhip_format_convert_create; returns n.
+ * channels: an integer, 2 .. 32 (the WAV pair: 1 .. 32); anything else is refused at creation.
+ *
+ * They run through lrhip_stage_execute_device alone, and the many-ported side of the call is a PORT TABLE, a small structure in HOST memory:
+ *
+ *     { uint32_t magic;            0x5450524c, the bytes "LRPT"
+ *       uint32_t count;            the stage's channel count
+ *       void    *ptr[count]; }     ptr[k]: the DEVICE address of port k
+ *
+ *   N-input stage  (interleave, wavpack):      in_dev  = the address of the table, n_in = samples per port; out_dev a device vector.
+ *   N-output stage (deinterleave, wavunpack):  out_dev = the address of the table, out_capacity = the capacity of EACH port; in_dev a device vector.
+ *
+ * The library reads the table on the host before anything is launched and refuses, with its own lrhip_strerror() message, a wrong magic, a
+ * count other than the stage's channels and a null pointer.  The pointers travel to the kernel by value in its argument block: nothing is
+ * copied to the device, no device-side table exists, and the table may be freed as soon as the call returns.  Ports may have any alignment;
+ * a port that is 16-byte aligned is moved 16 bytes per lane.  lrhip_stage_execute (host buffers), lrhip_stage_execute2* and
+ * lrhip_chain_create* refuse these stages.  (The table is a documented layout, not a declared type: luaradio_amd/_lib.py port_table() builds it.) */
 /* DelayBlock (radio/blocks/signal/delay.lua:26-72): delay by num_samples (> 0), zero initial state. elem_size 8 or 4. */
 lrhip_stage_t *lrhip_delay_create(unsigned num_samples, int elem_size);
 /* HilbertTransformBlock (radio/blocks/signal/hilberttransform.lua:25-37, :100-160): Float32 in, ComplexFloat32 out =

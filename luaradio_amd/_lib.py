@@ -119,6 +119,24 @@ CHAIN_EXACT_ROTATOR, CHAIN_NO_POLYPHASE_TAIL, CHAIN_NO_FUSION, CHAIN_NO_SINGLE_L
 CHAIN_EXACT = CHAIN_EXACT_ROTATOR | CHAIN_NO_POLYPHASE_TAIL | CHAIN_NO_SINGLE_LAUNCH
 
 
+# the port table of the many-ported stages (include/lrhip.h "Port tables"): { uint32 magic; uint32 count; void *ptr[count]; } in host memory
+PORT_TABLE_MAGIC = 0x5450524C          # "LRPT" in memory
+MAX_PORTS = 32
+
+
+def port_table_type(count):
+    """the ctypes mirror of a port table of `count` ports"""
+    class PortTable(C.Structure):
+        _fields_ = [("magic", C.c_uint32), ("count", C.c_uint32), ("ptr", C.c_void_p * count)]
+    return PortTable
+
+
+def port_table(ptrs):
+    """a port table of the device addresses `ptrs`; keep the object alive across the call and pass C.addressof(table) as the buffer"""
+    ptrs = list(ptrs)
+    return port_table_type(len(ptrs))(PORT_TABLE_MAGIC, len(ptrs), (C.c_void_p * len(ptrs))(*[int(p) if p else None for p in ptrs]))
+
+
 def load():
     """dlopen liblrhip.so and declare every entry point. Raises LrhipError if the library is absent."""
     global _lib

@@ -1130,3 +1130,157 @@ class QuadratureAmplitudeModulatorBlock(_ModulatorBlock):
 
     def _default_table(self):
         return qam_constellation(self.points)
+
+
+# ---- many-ported blocks (luaradio_amd/csrc/stage_interleave.h).  The side of the call with several ports travels as a port table
+# (_lib.port_table), the stages run through lrhip_stage_execute_device alone.
+MAX_CHANNELS = _lib.MAX_PORTS
+
+
+def interleave_op(name, num_channels, size):
+    return "%s:channels=%d:size=%d" % (name, num_channels, size)
+
+
+def deinterleave_plan(index, num_channels, n):
+    """DeinterleaveBlock's carried index as a rotation of the port table (deinterleave.lua:49-63): for a call of n samples, table entry j
+    (the port that receives samples j, j + N, ...) is channel (j + index) mod N.  Returns (channel of every table entry, samples of every
+    CHANNEL - the reference's ceil((n - offset) / N) with offset = (channel - index) mod N -, the index after the call)."""
+    N = num_channels
+    order = [(j + index) % N for j in range(N)]
+    counts = [max(0, -(-(n - ((c - index) % N)) // N)) for c in range(N)]
+    return order, counts, (index + n) % N
+
+
+class _Scratch:
+    """device vectors of one host-side process() call (lrhip_malloc), freed when the call ends"""
+
+    def __init__(self):
+        self.L, self.ptrs = _lib.load(), []
+
+    def alloc(self, nbytes):
+        p = _lib.check_ptr(self.L.lrhip_malloc(max(int(nbytes), 16)), "lrhip_malloc")
+        self.ptrs.append(p)
+        return p
+
+    def upload(self, x):
+        import ctypes as C
+        p = self.alloc(x.nbytes)
+        if x.nbytes:
+            _lib.check(self.L.lrhip_memcpy_h2d(p, x.ctypes.data_as(C.c_void_p), x.nbytes), "h2d")
+        return p
+
+    def download(self, p, count, dtype):
+        import ctypes as C
+        y = np.empty(count, dtype)
+        if y.nbytes:
+            _lib.check(self.L.lrhip_memcpy_d2h(y.ctypes.data_as(C.c_void_p), p, y.nbytes), "d2h")
+        return y
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.ptrs:
+            self.L.lrhip_free(p)
+        self.ptrs = []
+
+
+class _PortBlock(Block):
+    """a block whose stage has several input ports (_many_in) or several output ports"""
+    _many_in = True
+
+    def _create(self, op):
+        self._op = op
+        self._set_stage(_lib.load().lrhip_unary_create(op.encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % op.split(":")[0])
+
+    def process_device_ports(self, ins, n_in, outs, out_capacity):
+        """one device call: `ins` and `outs` are lists of device addresses, one per port; the list of the many-ported side becomes the port
+        table.  n_in counts samples per input port, out_capacity is the capacity of each output port.  Returns the stage's count."""
+        import ctypes as C
+        table = _lib.port_table(ins if self._many_in else outs)
+        at = C.addressof(table)
+        got = _lib.load().lrhip_stage_execute_device(self.stage_handle(), at if self._many_in else ins[0], n_in, outs[0] if self._many_in else at, out_capacity)
+        return _lib.check(got, "%s:process_device_ports" % self.name)
+
+    def _same_length(self, xs, dtype):
+        xs = [np.ascontiguousarray(x) for x in xs]
+        if len(xs) != self.num_channels or any(x.dtype != dtype or len(x) != len(xs[0]) for x in xs):
+            raise TypeError("Block %s expects %d %s vectors of equal length" % (self.name, self.num_channels, np.dtype(dtype).name))
+        return xs
+
+
+class InterleaveBlock(_PortBlock):
+    """radio/blocks/signal/interleave.lua. InterleaveBlock([num_channels=2]): in1 .. inN (Float32 or ComplexFloat32) -> out,
+    out[N i + k] = in_k[i].  The samples are moved as bytes (NaN payloads survive)."""
+    name = "InterleaveBlock"
+
+    def instantiate(self, num_channels=2):
+        self.num_channels = 2 if num_channels is None else num_channels
+        assert self.num_channels > 1, "Number of channels must be greater than 1"
+        assert isinstance(self.num_channels, int) and self.num_channels <= MAX_CHANNELS, "Number of channels must be an integer of at most %d" % MAX_CHANNELS
+        for t in (types.Float32, types.ComplexFloat32):
+            self.add_type_signature([Input("in%d" % (i + 1), t) for i in range(self.num_channels)], [Output("out", t)])
+
+    def op(self):
+        return interleave_op("interleave", self.num_channels, self.get_input_type().size)
+
+    def initialize(self):
+        self._create(self.op())
+
+    def process(self, *xs):
+        dt = self.get_input_type().dtype
+        xs = self._same_length(xs, dt)
+        n = len(xs[0])
+        with _Scratch() as s:
+            out = s.alloc(n * self.num_channels * dt.itemsize)
+            got = self.process_device_ports([s.upload(x) for x in xs], n, [out], n * self.num_channels)
+            return s.download(out, got, dt)
+
+
+class DeinterleaveBlock(_PortBlock):
+    """radio/blocks/signal/deinterleave.lua. DeinterleaveBlock([num_channels=2]): in (Float32 or ComplexFloat32) -> out1 .. outN,
+    out_j[i] = in[N i + j] over the whole stream: the position in the frame is carried across calls (`index`, as in the reference) and a
+    call may end anywhere in a frame.  process(x) returns a tuple of N vectors, whose lengths differ by at most one."""
+    name = "DeinterleaveBlock"
+    _many_in = False
+
+    def instantiate(self, num_channels=2):
+        self.num_channels = 2 if num_channels is None else num_channels
+        assert self.num_channels > 1, "Number of channels must be greater than 1"
+        assert isinstance(self.num_channels, int) and self.num_channels <= MAX_CHANNELS, "Number of channels must be an integer of at most %d" % MAX_CHANNELS
+        for t in (types.Float32, types.ComplexFloat32):
+            self.add_type_signature([Input("in", t)], [Output("out%d" % (i + 1), t) for i in range(self.num_channels)])
+        self.index = 0
+
+    def op(self):
+        return interleave_op("deinterleave", self.num_channels, self.get_input_type().size)
+
+    def initialize(self):
+        self.index = 0
+        self._create(self.op())
+
+    def reset(self):
+        self.index = 0
+        super().reset()
+
+    def max_output(self, n_in):
+        return -(-n_in // self.num_channels)
+
+    def process_device_channels(self, in_ptr, n_in, out_ptrs, out_capacity):
+        """one device call on the stream: out_ptrs[c] is the vector of CHANNEL c; returns the samples each channel received"""
+        order, counts, index = deinterleave_plan(self.index, self.num_channels, n_in)
+        if n_in:
+            self.process_device_ports([in_ptr], n_in, [out_ptrs[c] for c in order], out_capacity)
+        self.index = index
+        return counts
+
+    def process(self, x):
+        dt = self.get_input_type().dtype
+        x = np.ascontiguousarray(x)
+        if x.dtype != dt:
+            raise TypeError("Block %s expects %s input, got %s" % (self.name, self.get_input_type(), x.dtype))
+        cap = self.max_output(len(x))
+        with _Scratch() as s:
+            outs = [s.alloc(cap * dt.itemsize) for _ in range(self.num_channels)]
+            counts = self.process_device_channels(s.upload(x), len(x), outs, cap)
+            return tuple(s.download(p, c, dt) for p, c in zip(outs, counts))

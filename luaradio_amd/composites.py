@@ -474,12 +474,13 @@ def am_synchronous_receiver(rate=1102500.0, ifreq=50e3, bandwidth=5e3):
     return g.initialize()
 
 
-def wbfm_stereo_receiver(rate=1102500.0, tune_offset=-250e3):
+def wbfm_stereo_receiver(rate=1102500.0, tune_offset=-250e3, interleaved=False):
     """The compute blocks of examples/rtlsdr_wbfm_stereo.lua:13-33 as a DeviceGraph with one input "in" (ComplexFloat32 at `rate`):
     Tuner(offset, 200e3, 5) -> FrequencyDiscriminator(1.25) -> Hilbert(129), whose output feeds Delay(129) and the pilot branch
     ComplexBandpass(129, {18e3, 20e3}) -> PLL(100, 18950, 19050, 2).  L+R = Lowpass(128, 15e3) -> ComplexToReal of the delayed signal, L-R the same
     of MultiplyConjugate(delayed, pll); left = Add, right = Subtract, each -> FMDeemphasis(75e-6) -> Downsampler(5).
-    g.process(**{"in": x}) returns {"left": audio, "right": audio}."""
+    g.process(**{"in": x}) returns {"left": audio, "right": audio}; with interleaved=True left and right feed an InterleaveBlock(2) on the
+    device and the result is {"stereo": audio} - L R L R ..., what a two-channel WAVFileSink writes."""
     from .graph import DeviceGraph
     g = DeviceGraph()
     src = g.input("in", types.ComplexFloat32, rate)
@@ -502,6 +503,11 @@ def wbfm_stereo_receiver(rate=1102500.0, tune_offset=-250e3):
     g.connect(lmr_am_demod, "out", r_subtractor, "in2")
     g.connect(l_summer, B.FMDeemphasisFilterBlock(75e-6), l_downsampler)
     g.connect(r_subtractor, B.FMDeemphasisFilterBlock(75e-6), r_downsampler)
+    if interleaved:
+        stereo = B.InterleaveBlock(2)
+        stereo.name = "stereo"
+        g.connect(l_downsampler, "out", stereo, "in1")
+        g.connect(r_downsampler, "out", stereo, "in2")
     return g.initialize()
 
 

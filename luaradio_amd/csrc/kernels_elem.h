@@ -263,17 +263,23 @@ __device__ __forceinline__ T byteswap_raw(T v)
 }
 
 // RAW = storage integer type, VAL = the value type it is reinterpreted as (int8_t ... double)
+// one raw scalar -> Float32: the arithmetic of every source kernel (format_convert_*_kernel here, wavunpack in kernels_interleave.h)
+template <typename RAW, typename VAL, bool SWAP>
+__device__ __forceinline__ float format_convert_value(RAW r, double offset, double scale)
+{
+    if (SWAP) r = byteswap_raw(r);
+    VAL v;
+    __builtin_memcpy(&v, &r, sizeof(v));
+    return (float)(((double)v - offset) / scale);
+}
+
 template <typename RAW, typename VAL, bool SWAP>
 __global__ __launch_bounds__(256) void format_convert_kernel(const RAW *__restrict__ in, float *__restrict__ out, unsigned long n,
                                                              double offset, double scale)
 {
     unsigned long stride = (unsigned long)gridDim.x * blockDim.x;
     for (unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        RAW r = in[i];
-        if (SWAP) r = byteswap_raw(r);
-        VAL v;
-        __builtin_memcpy(&v, &r, sizeof(v));
-        out[i] = (float)(((double)v - offset) / scale);
+        out[i] = format_convert_value<RAW, VAL, SWAP>(in[i], offset, scale);
     }
 }
 
@@ -287,12 +293,7 @@ __global__ __launch_bounds__(256) void format_convert_vec_kernel(const RAW *__re
                                                                  double offset, double scale)
 {
     __shared__ float lut[sizeof(RAW) == 1 ? 256 : 1];
-    auto conv = [&](RAW r) {
-        if (SWAP) r = byteswap_raw(r);
-        VAL v;
-        __builtin_memcpy(&v, &r, sizeof(v));
-        return (float)(((double)v - offset) / scale);
-    };
+    auto conv = [&](RAW r) { return format_convert_value<RAW, VAL, SWAP>(r, offset, scale); };
     if (sizeof(RAW) == 1) {
         lut[threadIdx.x] = conv((RAW)threadIdx.x);
         __syncthreads();
@@ -344,24 +345,30 @@ __device__ __forceinline__ uint32_t pack_u32_low(double v)
     return (uint32_t)(t - ldexp(floor(ldexp(t, -32)), 32));
 }
 
+// one Float32 -> one raw scalar: the arithmetic of every sink kernel (format_pack_kernel here, wavpack in kernels_interleave.h)
+template <typename RAW, typename VAL, bool SWAP>
+__device__ __forceinline__ RAW format_pack_value(float x, double offset, double scale)
+{
+#pragma clang fp contract(off)
+    const double p = (double)x * scale;
+    const double d = p + offset;
+    VAL v;
+    if constexpr (std::is_floating_point<VAL>::value) v = (VAL)d;
+    else if constexpr (std::is_same<VAL, uint32_t>::value) v = pack_u32_low(d);
+    else v = (VAL)pack_i32(d);                      // the low bytes of the int32_t (two's complement)
+    RAW r;
+    __builtin_memcpy(&r, &v, sizeof(r));
+    if (SWAP) r = byteswap_raw(r);
+    return r;
+}
+
 template <typename RAW, typename VAL, bool SWAP>
 __global__ __launch_bounds__(256) void format_pack_kernel(const float *__restrict__ in, RAW *__restrict__ out, unsigned long n,
                                                           double offset, double scale)
 {
-#pragma clang fp contract(off)
     unsigned long stride = (unsigned long)gridDim.x * blockDim.x;
-    for (unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const double p = (double)in[i] * scale;
-        const double d = p + offset;
-        VAL v;
-        if constexpr (std::is_floating_point<VAL>::value) v = (VAL)d;
-        else if constexpr (std::is_same<VAL, uint32_t>::value) v = pack_u32_low(d);
-        else v = (VAL)pack_i32(d);                      // the low bytes of the int32_t (two's complement)
-        RAW r;
-        __builtin_memcpy(&r, &v, sizeof(r));
-        if (SWAP) r = byteswap_raw(r);
-        out[i] = r;
-    }
+    for (unsigned long i = (unsigned long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        out[i] = format_pack_value<RAW, VAL, SWAP>(in[i], offset, scale);
 }
 
 // ------------------------------------------------------------------------------------------------

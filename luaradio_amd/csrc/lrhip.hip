@@ -36,6 +36,7 @@
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
 #include "kernels_pll.h"
+#include "kernels_interleave.h"
 
 using namespace lrhip;
 
@@ -66,6 +67,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_preamble.h"
 #include "stage_framers.h"
 #include "stage_modulator.h"
+#include "stage_interleave.h"
 #include "chain_plan.h"
 
 // =====================================================================================================
@@ -413,6 +415,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "preamblesampler") return preamblesampler_create(op);
         // the modulators carry their symbol table as a list (stage_modulator.h)
         if (head == "pam" || head == "qam") return modulator_create(op);
+        // the many-ported stages, whose other side is a port table (stage_interleave.h)
+        if (head == "interleave" || head == "deinterleave" || head == "wavpack" || head == "wavunpack") return port_stage_create(op);
         // the PLL names its output port in words (stage_pll.h)
         if (head == "pll") return pll_create(op);
         // the five framers take no parameters at all (stage_framers.h)
@@ -583,6 +587,7 @@ long lrhip_stage_execute_device(lrhip_stage_t *q, const void *in_dev, unsigned l
 long lrhip_stage_execute(lrhip_stage_t *q, const void *in_host, unsigned long n_in, void *out_host, unsigned long out_capacity)
 {
     if (!q) return set_error("null stage");
+    if (dynamic_cast<PortStage *>(q)) return set_error("%s stage takes a port table of device pointers: use lrhip_stage_execute_device", q->kind());
     return host_execute(q->h_in, q->h_out, q->d_in, q->d_out, q->in_size, q->out_size, q->max_output(n_in), in_host, n_in,
                         out_host, out_capacity,
                         [&](const void *di, unsigned long n, void *dout, unsigned long cap) { return q->run(di, n, dout, cap); }, q->align(), q->direct_io_ok());
@@ -630,6 +635,8 @@ lrhip_chain_t *lrhip_chain_create_ex(lrhip_stage_t **stages, unsigned nstages, u
     }
     for (unsigned i = 0; i < nstages; i++)
         if (!stages[i]) { set_error("chain: stage %u is null", i); return nullptr; }
+    for (unsigned i = 0; i < nstages; i++)
+        if (dynamic_cast<PortStage *>(stages[i])) { set_error("chain: stage %u (%s) takes a port table and cannot be part of a chain", i, stages[i]->kind()); return nullptr; }
     for (unsigned i = 0; i + 1 < nstages; i++)
         if (stages[i]->out_size != stages[i + 1]->in_size) {
             set_error("chain: stage %u (%s) emits %d-byte samples but stage %u (%s) takes %d-byte samples", i, stages[i]->kind(),

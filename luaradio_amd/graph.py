@@ -5,8 +5,9 @@ explicit-port forms (composite.lua:140-330), type differentiation and rate propa
 (:426-470 _prepare_to_run), and the synchronous one-process variant of run (:626-700 run(false): every block's
 process() is called once per input chunk, upstream first).  What the reference moves through socketpairs
 (radio/core/pipe.lua) stays in HBM here: a block's output vector is a device buffer that its consumers read in
-place; a linear run of blocks becomes one lrhip_chain_t (kernel fusion), a two-input block waits for the shorter of
-its inputs and keeps the excess of the other for the next call, like a pipe would.
+place; a linear run of blocks becomes one lrhip_chain_t (kernel fusion), a block with several inputs waits for the shortest of
+its inputs and keeps the excess of the others for the next call, like a pipe would.  A block whose one stage has more than two inputs or
+several outputs (InterleaveBlock, DeinterleaveBlock, WAVFileSink) runs in one call through a port table; a block without outputs is a sink.
 
     g = DeviceGraph()
     src1, src2 = g.input("a", types.ComplexFloat32, rate=1e6), g.input("b", types.ComplexFloat32, rate=1e6)
@@ -22,6 +23,7 @@ import numpy as np
 
 from . import _lib
 from .block import Block, Output
+from .blocks import _PortBlock
 from .composites import Chain, CompositeBlock
 
 
@@ -263,7 +265,22 @@ class DeviceGraph:
             else:
                 ptrs, count = self._gather(n)
             subs = getattr(b, "_sub_blocks", None)
-            if subs:                                     # one input, several outputs (ComplexToFloatBlock)
+            if isinstance(b, _PortBlock):                # several ports on one side of ONE stage call: the port table (blocks.py)
+                tail = n
+                if not n.out:                            # a sink (WAVFileSink): records into a device buffer, copied down and written
+                    b.write_device(ptrs, count)
+                elif b._many_in:                         # InterleaveBlock
+                    cap = b.max_output(count)
+                    n.out[0][0].reserve(max(cap, 1) * b.get_output_type().size)
+                    n.out[0][1] = b.process_device_ports(ptrs, count, [n.out[0][0].ptr], cap) if count else 0
+                else:                                    # DeinterleaveBlock: every output in the one call, each with its own count
+                    cap = b.max_output(count)
+                    for k in range(len(n.out)):
+                        n.out[k][0].reserve(max(cap, 1) * b.get_output_type(k + 1).size)
+                    counts = b.process_device_channels(ptrs[0], count, [o[0].ptr for o in n.out], cap)
+                    for k, c in enumerate(counts):
+                        n.out[k][1] = c
+            elif subs:                                   # one input, several outputs (ComplexToFloatBlock)
                 for k, sb in enumerate(subs):
                     cap = sb.max_output(count)
                     n.out[k][0].reserve(max(cap, 1) * sb.get_output_type().size)
