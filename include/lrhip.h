@@ -270,6 +270,31 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
+ *   "signalsource:signal=exponential|cosine|sine|square|triangle|sawtooth|constant:frequency=F:rate=R:amplitude=A:phase=P:offset=O"
+ *                                                      (sources/signal.lua) a SOURCE: no input, lrhip_stage_input_size() = 0; ComplexFloat32 for
+ *                                                      exponential, Float32 otherwise.  Every key once; doubles as %.17g text, finite, R > 0.  Sample n
+ *                                                      is a closed form of the absolute index: turns(n) = p0 + n step in wrapping uint64 arithmetic,
+ *                                                      with fx(x) = uint64(rint(ldexp(x - floor(x), 64))) mod 2^64, step = fx(F / R),
+ *                                                      p0 = fx(P / 6.283185307179586).  exponential: A (c, s), the translator's phasor of turns(n), O
+ *                                                      ignored; cosine: c A + O; sine: s A + O; with td = (turns >> 11) 2^-53 and first = turns < 2^63,
+ *                                                      square: w = first ? 1 : -1, triangle: w = first ? 1 - 4 td : 4 td - 3, sawtooth: w = 2 td - 1,
+ *                                                      the sample w A + O; constant: A alone.  One double multiply and one double add, rounded once
+ *                                                      to Float32.  The reference adds omega to a running double phase, wraps it once per 8192-sample
+ *                                                      chunk and takes cosf / sinf of the phase rounded to Float32: its own output is off the exact
+ *                                                      waveform by up to A ulp_f32(2 pi + 8192 omega) / 2 (signal_spec.lua's 2e-5 epsilon), and it
+ *                                                      cannot be cut or sought.  Here any chunking gives the same bits, lrhip_stage_seek(n0) sets the
+ *                                                      index, reset puts it back to 0, memory() = 0, rate 1 : 1, max_output(n) = n.
+ *   "uniformrandomsource:type=cf32|f32|byte|bit:lo=L:hi=H:seed=S"
+ *                                                      (sources/uniformrandom.lua) a SOURCE of ComplexFloat32, Float32, Byte or Bit samples; L <= H
+ *                                                      finite doubles (Byte: integers in 0 .. 255; Bit: ignored), S a decimal uint64.  Word j of the
+ *                                                      stream is output j & 3 of Philox4x32-10 with counter (lo32(j >> 2), hi32(j >> 2), 0, 0) and key
+ *                                                      (lo32(S), hi32(S)); u(j) = w(j) 2^-32.  f32: float(L + (H - L) u(n)) in double, not contracted;
+ *                                                      cf32: re from w(2 n), im from w(2 n + 1); byte: L + ((w(n) (H - L + 1)) >> 32); bit: w(n) >> 31.
+ *                                                      The reference draws from LuaJIT's sequential math.random, whose values nobody relies on: the
+ *                                                      contract is distribution, range and determinism per seed.  Chunking, seek, reset, memory() as
+ *                                                      the signal source.
+ * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
+ * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time
  * partitions. */
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex);
@@ -342,7 +367,7 @@ lrhip_stage_t *lrhip_pfb_oversampled_create(const float *taps, unsigned ntaps, u
 void lrhip_stage_destroy(lrhip_stage_t *q);
 /* Back to the just-created state (zero history, phase 0, index 0). */
 int lrhip_stage_reset(lrhip_stage_t *q);
-/* Bytes per input / output sample (8 or 4). */
+/* Bytes per input / output sample (8 or 4; 1 for Bit / Byte streams, the record size for raw records and frames; input 0: a source). */
 int lrhip_stage_input_size(const lrhip_stage_t *q);
 int lrhip_stage_output_size(const lrhip_stage_t *q);
 /* Upper bound on the samples execute() will write for n_in inputs, so the caller can
@@ -385,7 +410,13 @@ long lrhip_stage_execute2_device(lrhip_stage_t *q, const void *in1_dev, const vo
  *      rather than bit for bit;
  *   5. consecutive overlap-save filters on a ComplexFloat32 stream merged into ONE filter with the taps convolved in double (up to 1 281
  *      taps): rounds once where the cascade rounds per stage, <= 1e-6 of the exact cascade.
- * lrhip_chain_create_ex() below switches 2-5 off per chain (LRHIP_CHAIN_EXACT); 1 is chosen per filter (use_fft = 0: direct form). */
+ * lrhip_chain_create_ex() below switches 2-5 off per chain (LRHIP_CHAIN_EXACT); 1 is chosen per filter (use_fft = 0: direct form).
+ *
+ * A SOURCE (lrhip_stage_input_size() = 0: "signalsource", "uniformrandomsource") may be the FIRST stage of a chain, nowhere else.  Such a chain has no input:
+ * lrhip_chain_execute, _execute_device and lrhip_chain_submit take in = NULL and n_in = the number of samples to generate, and copy nothing to the device;
+ * the source runs as a launch of its own (it fuses with nothing).  The ring (set_ring / submit / collect), seek, halo, shard_align and start_at work as
+ * for any chain - the input samples start_at drops are the generated ones.  The entry points that move input bytes - lrhip_chain_push,
+ * lrhip_chain_ring_input, lrhip_chain_submit_fd - refuse it with a message. */
 lrhip_chain_t *lrhip_chain_create(lrhip_stage_t **stages, unsigned nstages);
 /* The numerical contract per chain (what a LuaRadio script sets as DeviceChainBlock.exact, lua/radio/composites/devicechain.lua).
  * lrhip_chain_create(stages, n) == lrhip_chain_create_ex(stages, n, 0).  Flags:

@@ -29,9 +29,11 @@ class Chain:
         L = _lib.load()
         arr = (C.c_void_p * len(self.blocks))(*[b.stage_handle() for b in self.blocks])
         self._chain = _lib.check_ptr(L.lrhip_chain_create_ex(arr, len(self.blocks), self.flags), "Creating lrhip chain object")
+        # a chain may start with a generator source (SignalSource, UniformRandomSource): it has no input and is run by count - generate(n), submit(n)
+        self.source = bool(getattr(self.blocks[0], "is_source", False))
         # a chain may start with a file source's format stage: its input is then RAW file records (uint8, record_size bytes each)
         self.in_record = getattr(self.blocks[0], "record_size", None)
-        self.in_type = None if self.in_record else self.blocks[0].get_input_type()
+        self.in_type = None if self.in_record or self.source else self.blocks[0].get_input_type()
         self.out_type = self.blocks[-1].get_output_type()
 
     def __del__(self):
@@ -78,6 +80,8 @@ class Chain:
 
     def _count(self, x):
         """input vector -> (contiguous array, number of input samples)"""
+        if self.source:
+            raise TypeError("chain starts with %s and takes no input: use generate(n), submit(n) or stream(counts)" % self.blocks[0].name)
         x = np.ascontiguousarray(x)
         if self.in_record:
             if x.dtype != np.uint8 or len(x) % self.in_record:
@@ -96,7 +100,20 @@ class Chain:
         _lib.check(n, "chain:process")
         return out[:n]
 
+    def generate(self, n):
+        """a chain that starts with a generator source: the output of its next n generated samples (lrhip_chain_execute with a null input)"""
+        if not self.source:
+            raise TypeError("generate() needs a chain that starts with a generator source: use process(x)")
+        L = _lib.load()
+        n = int(n)
+        cap = L.lrhip_chain_max_output(self._chain, n)
+        out = np.empty(cap, dtype=self.out_type.dtype)
+        got = L.lrhip_chain_execute(self._chain, None, n, out.ctypes.data_as(C.c_void_p), cap)
+        _lib.check(got, "chain:generate")
+        return out[:got]
+
     def process_device(self, in_ptr, n_in, out_ptr, out_capacity):
+        """(a chain that starts with a generator source: in_ptr None, n_in the number of samples to generate)"""
         n = _lib.load().lrhip_chain_execute_device(self._chain, in_ptr, n_in, out_ptr, out_capacity)
         return _lib.check(n, "chain:process_device")
 
@@ -113,6 +130,11 @@ class Chain:
         self._ring_out = np.empty(L.lrhip_chain_push_bound(self._chain, max_chunk), dtype=self.out_type.dtype)
 
     def submit(self, x):
+        """one chunk into the ring: an input vector - or, for a chain that starts with a generator source, the number of samples to generate"""
+        if self.source:
+            if not isinstance(x, (int, np.integer)):
+                raise TypeError("chain starts with %s and takes no input: submit(n) takes a count" % self.blocks[0].name)
+            return _lib.check(_lib.load().lrhip_chain_submit(self._chain, None, int(x)), "chain:submit")
         x, count = self._count(x)
         return _lib.check(_lib.load().lrhip_chain_submit(self._chain, x.ctypes.data_as(C.c_void_p), count), "chain:submit")
 
@@ -127,6 +149,8 @@ class Chain:
         """numpy view (uint8 for raw-record chains, else the input dtype) of the pinned buffer the next submit() will use:
         fill it in place (file.readinto(view), socket.recv_into(view)) and submit(view[:n]) - no staging copy.  None when the
         ring is full."""
+        if self.source:
+            raise TypeError("chain starts with %s and takes no input: there is no ring input to fill" % self.blocks[0].name)
         p = _lib.load().lrhip_chain_ring_input(self._chain)
         if not p:
             return None
@@ -144,7 +168,8 @@ class Chain:
         return _lib.load().lrhip_chain_in_flight(self._chain)
 
     def stream(self, chunks):
-        """Run an iterable of input vectors through the ring (one slot per vector), yielding the outputs in order."""
+        """Run an iterable of input vectors (counts for a chain that starts with a generator source) through the ring, one slot each,
+        yielding the outputs in order."""
         for x in chunks:
             if self.in_flight == self._ring_depth:
                 yield self.collect()

@@ -125,8 +125,8 @@ static long host_execute(PinnedBuf &h_in, PinnedBuf &h_out, DeviceBuf &d_in, Dev
                          unsigned long max_out, const void *in_host, unsigned long n_in, void *out_host,
                          unsigned long out_capacity, Runner run, unsigned long align = 1, bool direct_ok = false)
 {
-    if (n_in && !in_host) return set_error("null input buffer");
-    size_t in_bytes = (size_t)n_in * in_size;
+    if (n_in && !in_host && in_size) return set_error("null input buffer");
+    size_t in_bytes = (size_t)n_in * in_size;           // in_size 0: a source (or a chain headed by one) generates n_in samples, nothing travels to the device
     unsigned long cap = max_out < out_capacity ? max_out : out_capacity;
     if (max_out > out_capacity) return set_error("output capacity %lu < required %lu", out_capacity, max_out);
     if (max_out && !out_host) return set_error("null output buffer");
@@ -189,7 +189,7 @@ static long host_execute(PinnedBuf &h_in, PinnedBuf &h_out, DeviceBuf &d_in, Dev
         const unsigned long n_k = k + 1 == pieces ? n_in - done_in : per;
         const size_t ib = (size_t)done_in * in_size, nb = (size_t)n_k * in_size;
         if (!in_reg) host_copy((char *)h_in.p + ib, (const char *)in_host + ib, nb);
-        LR_HIP(hipMemcpyAsync((char *)d_in.p + ib, (in_reg ? (const char *)in_host : (const char *)h_in.p) + ib, nb, hipMemcpyHostToDevice, hp.s_in));
+        if (nb) LR_HIP(hipMemcpyAsync((char *)d_in.p + ib, (in_reg ? (const char *)in_host : (const char *)h_in.p) + ib, nb, hipMemcpyHostToDevice, hp.s_in));
         LR_HIP(hipEventRecord(hp.ev[3 * k], hp.s_in));
         LR_HIP(hipStreamWaitEvent(ctx().stream, hp.ev[3 * k], 0));
         // (capacity: what is left of the whole call's bound plus the slack reserved above - a piece's own bound may round up where the whole call's does not)

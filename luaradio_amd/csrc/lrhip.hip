@@ -37,6 +37,7 @@
 #include "kernels_modulator.h"
 #include "kernels_pll.h"
 #include "kernels_interleave.h"
+#include "kernels_source.h"
 
 using namespace lrhip;
 
@@ -68,6 +69,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_framers.h"
 #include "stage_modulator.h"
 #include "stage_interleave.h"
+#include "stage_source.h"
 #include "chain_plan.h"
 
 // =====================================================================================================
@@ -417,6 +419,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "pam" || head == "qam") return modulator_create(op);
         // the many-ported stages, whose other side is a port table (stage_interleave.h)
         if (head == "interleave" || head == "deinterleave" || head == "wavpack" || head == "wavunpack") return port_stage_create(op);
+        // the generator sources name their waveform / sample type in words and carry a 64-bit seed (stage_source.h)
+        if (head == "signalsource" || head == "uniformrandomsource") return source_create(op);
         // the PLL names its output port in words (stage_pll.h)
         if (head == "pll") return pll_create(op);
         // the five framers take no parameters at all (stage_framers.h)
@@ -580,7 +584,7 @@ unsigned long lrhip_stage_max_output(const lrhip_stage_t *q, unsigned long n_in)
 long lrhip_stage_execute_device(lrhip_stage_t *q, const void *in_dev, unsigned long n_in, void *out_dev, unsigned long out_capacity)
 {
     if (!q) return set_error("null stage");
-    if (n_in && (!in_dev || (!out_dev && q->max_output(n_in)))) return set_error("null buffer");
+    if (n_in && ((!in_dev && !q->is_source()) || (!out_dev && q->max_output(n_in)))) return set_error("null buffer");
     return q->run(in_dev, n_in, out_dev, out_capacity);
 }
 
@@ -637,6 +641,9 @@ lrhip_chain_t *lrhip_chain_create_ex(lrhip_stage_t **stages, unsigned nstages, u
         if (!stages[i]) { set_error("chain: stage %u is null", i); return nullptr; }
     for (unsigned i = 0; i < nstages; i++)
         if (dynamic_cast<PortStage *>(stages[i])) { set_error("chain: stage %u (%s) takes a port table and cannot be part of a chain", i, stages[i]->kind()); return nullptr; }
+    // a source has no input: it can only be the head of a chain, where n_in counts the samples to generate
+    for (unsigned i = 1; i < nstages; i++)
+        if (stages[i]->is_source()) { set_error("chain: stage %u (%s) is a source and can only be the first stage of a chain", i, stages[i]->kind()); return nullptr; }
     for (unsigned i = 0; i + 1 < nstages; i++)
         if (stages[i]->out_size != stages[i + 1]->in_size) {
             set_error("chain: stage %u (%s) emits %d-byte samples but stage %u (%s) takes %d-byte samples", i, stages[i]->kind(),
@@ -816,6 +823,13 @@ int lrhip_chain_set_ring(lrhip_chain_t *c, unsigned depth, unsigned long max_chu
     return 0;
 }
 
+// the entry points that move input BYTES have nothing to do for a chain whose first stage is a source: it is run by count (execute / submit with a null input)
+static int chain_refuse_source(const lrhip_chain *c, const char *what)
+{
+    const lrhip_stage *s = c->ops.front().stage;
+    return s->is_source() ? set_error("%s: the chain starts with a source (%s) and takes no input: call lrhip_chain_execute or lrhip_chain_submit with a "
+                                      "null input and the number of samples to generate", what, s->kind()) : 0;
+}
 static long chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_in, bool allow_inplace);
 long lrhip_chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_in) { return chain_submit(c, in_host, n_in, true); }
 static long chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_in, bool allow_inplace)
@@ -826,9 +840,9 @@ static long chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_
     if (c->inflight == c->ring.size()) return set_error("ring full: collect a chunk first (%u in flight)", c->inflight);
     if (c->fill) return set_error("chain has %lu pushed samples pending: flush before mixing submit() with push()", c->fill);
     lrhip_chain::Slot &sl = *c->ring[c->head];
-    if (n_in && !in_host) return set_error("null input buffer");
     int in_size = c->ops.front().stage->in_size, out_size = c->ops.back().stage->out_size;
-    size_t bytes = (size_t)n_in * in_size;
+    if (n_in && !in_host && in_size) return set_error("null input buffer");
+    size_t bytes = (size_t)n_in * in_size;             // a source at the head: nothing to copy, n_in samples are generated
     const void *zin = nullptr;           // input read in place across the link
     // the slot was collected (ev_out waited) before it can be reused, so its buffers are free on host and device
     if (bytes) {
@@ -844,7 +858,7 @@ static long chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_
         if (ring_direct && allow_inplace && c->ops.front().stage->direct_io_ok()) zin = direct ? host_ranges().device_ptr(in_host, bytes) : sl.h_in.p;
         if (!zin) LR_HIP(hipMemcpyAsync(sl.d_in.p, direct ? in_host : sl.h_in.p, bytes, hipMemcpyHostToDevice, c->s_in));
     }
-    if (!zin) {
+    if (!zin && in_size) {
         LR_HIP(hipEventRecord(sl.ev_in, c->s_in));
         LR_HIP(hipStreamWaitEvent(ctx().stream, sl.ev_in, 0));
     }
@@ -867,6 +881,7 @@ static long chain_submit(lrhip_chain_t *c, const void *in_host, unsigned long n_
 long lrhip_chain_submit_fd(lrhip_chain_t *c, int fd, unsigned long long offset, unsigned long max_in)
 {
     if (!c) return set_error("null chain");
+    if (chain_refuse_source(c, "lrhip_chain_submit_fd")) return -1;
     if (c->ring.empty()) return set_error("chain has no ring: call lrhip_chain_set_ring first");
     if (c->inflight == c->ring.size()) { set_error("ring full: collect a chunk first (%u in flight)", c->inflight); return -3; }
     if (c->fill) return set_error("chain has %lu pushed samples pending: flush before mixing submit() with push()", c->fill);
@@ -888,6 +903,7 @@ long lrhip_chain_submit_fd(lrhip_chain_t *c, int fd, unsigned long long offset, 
 void *lrhip_chain_ring_input(lrhip_chain_t *c)
 {
     if (!c) { set_error("null chain"); return nullptr; }
+    if (chain_refuse_source(c, "lrhip_chain_ring_input")) return nullptr;
     if (c->ring.empty()) { set_error("chain has no ring: call lrhip_chain_set_ring first"); return nullptr; }
     if (c->inflight == c->ring.size()) { set_error("ring full: collect a chunk first (%u in flight)", c->inflight); return nullptr; }
     return c->ring[c->head]->h_in.p;
@@ -983,6 +999,7 @@ unsigned long lrhip_chain_push_bound(const lrhip_chain_t *c, unsigned long n_in)
 long lrhip_chain_push(lrhip_chain_t *c, const void *in_host, unsigned long n_in, void *out_host, unsigned long out_capacity)
 {
     if (!c) return set_error("null chain");
+    if (chain_refuse_source(c, "lrhip_chain_push")) return -1;
     if (c->ring.empty()) return set_error("chain has no ring: call lrhip_chain_set_ring first");
     if (n_in && !in_host) return set_error("null input buffer");
     if (out_capacity < lrhip_chain_push_bound(c, n_in)) return set_error("output capacity %lu < lrhip_chain_push_bound() = %lu", out_capacity, lrhip_chain_push_bound(c, n_in));

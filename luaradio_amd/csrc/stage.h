@@ -6,7 +6,8 @@
 // stage base
 // =====================================================================================================
 struct lrhip_stage {
-    int in_size = 8, out_size = 8;     // bytes per sample
+    int in_size = 8, out_size = 8;     // bytes per sample; in_size 0: a source (stage_source.h), which has no input at all
+    bool is_source() const { return in_size == 0; }   // run(in, n, ...) ignores `in` and generates n samples
     int in2_size = 0;                  // two-input stages whose second input differs from the first (SamplerBlock's clock); 0 = in_size
     int input2_size() const { return in2_size ? in2_size : in_size; }
     PinnedBuf h_in, h_out;             // pinned staging for the host-pointer execute

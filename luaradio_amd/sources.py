@@ -320,3 +320,105 @@ class WAVFileSource(_PortBlock):
     def cleanup(self):
         if isinstance(self.file, str):
             self._fh.close()
+
+
+# ---- generator sources (csrc/stage_source.h): no input, sample n a closed form of the absolute index n -------------------------------------
+SIGNALS = {"exponential": types.ComplexFloat32, "cosine": types.Float32, "sine": types.Float32, "square": types.Float32,
+           "triangle": types.Float32, "sawtooth": types.Float32, "constant": types.Float32}          # signal.lua:40-48
+
+
+def signal_op(signal, frequency, rate, amplitude=1.0, phase=0.0, offset=0.0):
+    return "signalsource:signal=%s:frequency=%.17g:rate=%.17g:amplitude=%.17g:phase=%.17g:offset=%.17g" % (
+        signal, float(frequency), float(rate), float(amplitude), float(phase), float(offset))
+
+
+def uniform_random_op(type_name, lo, hi, seed):
+    return "uniformrandomsource:type=%s:lo=%.17g:hi=%.17g:seed=%d" % (type_name, float(lo), float(hi), int(seed))
+
+
+class _GeneratorSource(Block):
+    """a block whose stage has no input: process(n) generates the next n samples of the stream, seek(n0) moves to absolute sample n0"""
+    is_source = True
+
+    def op(self):
+        raise NotImplementedError
+
+    def get_rate(self):
+        return self.rate
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self.op().split(":")[0])
+
+    def process(self, n=None):
+        """the next n samples (chunk_size when n is None, the reference's chunk)"""
+        n = self.chunk_size if n is None else int(n)
+        out = np.empty(n, dtype=self.get_output_type().dtype)
+        got = _lib.load().lrhip_stage_execute(self.stage_handle(), None, n, out.ctypes.data_as(C.c_void_p), n)
+        _lib.check(got, "%s:process" % self.name)
+        return out[:got]
+
+    def process_device(self, out_ptr, n):
+        """the next n samples into device memory at out_ptr, asynchronous on the library stream"""
+        got = _lib.load().lrhip_stage_execute_device(self.stage_handle(), None, int(n), out_ptr, int(n))
+        return _lib.check(got, "%s:process_device" % self.name)
+
+
+class SignalSource(_GeneratorSource):
+    """radio/blocks/sources/signal.lua. SignalSource(signal, frequency, rate[, {amplitude=1, offset=0, phase=0}]): "exponential" gives
+    ComplexFloat32, "cosine", "sine", "square", "triangle", "sawtooth" and "constant" Float32.  The reference adds omega to a running double phase
+    and wraps it once per chunk; here the phase of sample n is n * frequency / rate + phase / 2 pi turns in exact 64-bit fixed point, so any chunking
+    gives the same bits and seek(n0) continues at sample n0 (include/lrhip.h has the closed forms)."""
+    name = "SignalSource"
+
+    def instantiate(self, signal=None, frequency=None, rate=None, options=None):
+        assert signal, "Missing argument #1 (signal)"
+        if signal not in SIGNALS:
+            raise AssertionError('Unsupported signal ("%s")' % (signal,))          # signal.lua:50
+        assert frequency is not None, "Missing argument #2 (frequency)"
+        assert rate, "Missing argument #3 (rate)"
+        self.signal, self.frequency, self.rate = signal, frequency, rate
+        self.options = dict(options or {})
+        self.chunk_size = 8192
+        self.add_type_signature([], [Output("out", SIGNALS[signal])])
+        self.signature = self.type_signatures[0]
+
+    def op(self):
+        o = self.options
+        return signal_op(self.signal, self.frequency, self.rate, 1.0 if o.get("amplitude") is None else o["amplitude"],
+                         o.get("phase") or 0.0, o.get("offset") or 0.0)
+
+
+_RANDOM_TYPES = {types.ComplexFloat32: "cf32", types.Float32: "f32", types.Byte: "byte", types.Bit: "bit"}
+
+
+class UniformRandomSource(_GeneratorSource):
+    """radio/blocks/sources/uniformrandom.lua. UniformRandomSource(data_type, rate[, {lo, hi}[, {seed=}]]): ComplexFloat32, Float32, Byte or Bit
+    samples drawn uniformly from [lo, hi] - [-1, 1] by default for the float types, [0, 255] for Byte (integers; the reference's own Byte default is
+    broken: `a = a or 0, b or 255` at uniformrandom.lua:56 leaves b nil), always {0, 1} for Bit.  The reference draws from LuaJIT's sequential
+    math.random; here word j of the stream is Philox4x32-10 of the absolute index and the seed (0 when none is given: the reference without a seed is
+    deterministic per run too), so the contract is distribution, range and determinism per seed, not LuaJIT's values, and any chunking or seek(n0)
+    gives the same bits."""
+    name = "UniformRandomSource"
+
+    def instantiate(self, data_type=None, rate=None, range=None, options=None):
+        assert data_type is not None, "Missing argument #1 (data_type)"
+        assert rate, "Missing argument #2 (rate)"
+        assert any(data_type is t for t in _RANDOM_TYPES), "Unsupported data type"          # uniformrandom.lua:73
+        self.data_type, self.rate = data_type, rate
+        lo, hi = (list(range or []) + [None, None])[:2]
+        if data_type is types.Byte:
+            lo, hi = 0 if lo is None else lo, 255 if hi is None else hi
+        elif data_type is types.Bit:
+            lo, hi = 0, 1
+        else:
+            lo, hi = -1.0 if lo is None else lo, 1.0 if hi is None else hi
+        self.range = (lo, hi)
+        seed = (options or {}).get("seed")
+        self.seed = 0 if seed is None else int(seed)
+        assert 0 <= self.seed < 1 << 64, "seed must be an integer in 0 .. 2^64 - 1"
+        self.chunk_size = 8192
+        self.add_type_signature([], [Output("out", data_type)])
+        self.signature = self.type_signatures[0]
+
+    def op(self):
+        return uniform_random_op(_RANDOM_TYPES[self.data_type], self.range[0], self.range[1], self.seed)

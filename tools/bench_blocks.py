@@ -167,6 +167,33 @@ def main():
         ms = timeit(lambda: gx.process(**{"in": xh}), reps=3)
         rows.append({"block": "ert_receiver(idm, scm, scm+) @ 2359296 (host vectors: copies in and out included)", "MS/s": round(m / ms / 1e3, 1), "ms": round(ms, 4),
                      "samples": m, "launches": sum(nd.runner.last_launches for nd in gx._order if nd.runner is not None)})
+    # the generator sources (kernels_source.h): write-only kernels, 8 / 4 / 1 bytes per sample and no read at all.  They alternate with the streaming
+    # yardstick (MultiplyConstant cf32, 8 B in + 8 B out per sample) on the same output buffer; the figure of merit is bytes moved per second over the
+    # yardstick's in the same runs, every run listed
+    if not only or any(t in "SignalSource UniformRandomSource" for t in only):
+        def source(blk):
+            blk.initialize()
+            return blk
+
+        mcs = mk(lr.MultiplyConstantBlock, [1.0], True)
+        cases = [("SignalSource exponential cf32", source(lr.SignalSource("exponential", 250e3, 2e6)), 8),
+                 ("SignalSource cosine f32", source(lr.SignalSource("cosine", 100e3, 1e6, {"amplitude": 2.5})), 4),
+                 ("SignalSource square f32", source(lr.SignalSource("square", 1e3, 2e6, {"offset": 1.0})), 4),
+                 ("UniformRandomSource cf32", source(lr.UniformRandomSource(types.ComplexFloat32, 1e6)), 8),
+                 ("UniformRandomSource f32", source(lr.UniformRandomSource(types.Float32, 1e6)), 4),
+                 ("UniformRandomSource bit", source(lr.UniformRandomSource(types.Bit, 1e3)), 1)]
+        runs = {name: [] for name, _, _ in cases}
+        runs["stream"] = []
+        for _ in range(4):
+            runs["stream"].append(timeit(lambda: mcs.process_device(xc.data_ptr(), n, out.data_ptr(), n)))
+            for name, src, _ in cases:
+                runs[name].append(timeit(lambda: src.process_device(out.data_ptr(), n)))
+        stream = sorted(runs["stream"])[len(runs["stream"]) // 2]
+        for name, key, bps in [("MultiplyConstant(1.0) cf32 (streaming yardstick, alternating with the sources)", "stream", 16)] + [(c[0], c[0], c[2]) for c in cases]:
+            ms_ = sorted(runs[key])[len(runs[key]) // 2]
+            rows.append({"block": name, "MS/s": round(n / ms_ / 1e3, 1), "bytes_per_sample": bps, "alg_GB/s": round(bps * n / ms_ / 1e6, 1),
+                         "frac_8TB/s": round(bps * n / ms_ / 1e6 / 8000, 4), "ms": round(ms_, 4), "ms_runs": [round(v, 4) for v in runs[key]],
+                         "bytes_per_s_over_streaming_yardstick": round((bps / ms_) / (16 / stream), 3)})
     if only and not any(t in "WBFM PSD Channelizer" for t in only):
         for r in rows:
             print(json.dumps(r))
