@@ -270,6 +270,18 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
+ *   "pfbsynthesizer:channels=K:oversample=R:taps=g0,g1,..."  (no block of the reference: the inverse of lrhip_pfb_oversampled_create) the K-channel synthesis
+ *                                                      filterbank in its polyphase + FFT form: K chains Upsampler(D) -> FIR(g) -> FrequencyTranslator(+c / K),
+ *                                                      D = K / R, summed, with zero history:  xhat[n] = sum_c exp(+j 2 pi c n / K) sum_m g[n - m D] Y[m, c].
+ *                                                      ComplexFloat32 -> ComplexFloat32.  The input is the frame stream the analysis bank emits (K values per
+ *                                                      frame, channel c at position c) and n_in counts VALUES: a call may end inside a frame, whose values
+ *                                                      are carried; a call emits D samples per frame it completes (max_output: ceil(n / K) D).  The domain
+ *                                                      is the analysis bank's: K a power of two in [8, 4096], K <= #taps <= min(64 K, 65536), R in {1, 2, 4};
+ *                                                      the taps as the "pam" table (%.9g or hexadecimal floating-point text).  Every output is one fmaf chain
+ *                                                      over the Q = ceil(#taps / D) frames under its taps, oldest first, so any chunking gives the same
+ *                                                      bytes; a non-finite value in frame m makes exactly outputs m D .. m D + #taps - 1 non-finite.
+ *                                                      Carried: the partial frame, the transformed last Q - 1 frames, the frame count modulo R; reset drops
+ *                                                      all three.  rate() = R : 1, memory() = -1, seek is refused.  Fuses with nothing.
  *   "signalsource:signal=exponential|cosine|sine|square|triangle|sawtooth|constant:frequency=F:rate=R:amplitude=A:phase=P:offset=O"
  *                                                      (sources/signal.lua) a SOURCE: no input, lrhip_stage_input_size() = 0; ComplexFloat32 for
  *                                                      exponential, Float32 otherwise.  Every key once; doubles as %.17g text, finite, R > 0.  Sample n

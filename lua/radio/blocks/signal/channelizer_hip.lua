@@ -61,7 +61,58 @@ function PolyphaseChannelizerBlock:initialize()
     self.out = types.ComplexFloat32.vector()
 end
 
-local M = {PolyphaseChannelizerBlock = PolyphaseChannelizerBlock}
+---
+-- PolyphaseSynthesizerBlock: the synthesis filterbank that undoes the channelizer - K parallel chains UpsamplerBlock(D) -> FIRFilterBlock(taps) ->
+-- FrequencyTranslatorBlock(+c * rate_out / K), c = 0 .. K-1, summed, D = K / oversample - in its polyphase + FFT form.  Input: the frame stream the
+-- channelizer emits (K ComplexFloat32 values per frame, channel c at position c; a vector may end inside a frame, whose values wait for the next one);
+-- output: D samples per completed frame, so the port carries rate / oversample samples per second.  K a power of two in [8, 4096],
+-- K <= #taps <= min(64 K, 65536).  The stage has no entry point of its own: it is created by name through lrhip_unary_create, its taps travelling in
+-- the name as %.9g text, which gives every Float32 back exactly.
+--
+--     local PolyphaseSynthesizerBlock = require('radio.blocks.signal.channelizer_hip').PolyphaseSynthesizerBlock
+--     top:connect(channelizer, PolyphaseSynthesizerBlock(64, taps, {oversample = 2}), sink)
+--
+-- @block PolyphaseSynthesizerBlock
+-- @tparam int num_channels Number of channels K
+-- @tparam array|vector taps Real-valued prototype lowpass taps
+-- @tparam[opt={}] table options Additional options, specifying:
+--                         * `oversample` (int, 1, 2 or 4; default 1)
+
+local PolyphaseSynthesizerBlock = block.factory("PolyphaseSynthesizerBlock")
+
+function PolyphaseSynthesizerBlock:instantiate(num_channels, taps, options)
+    assert(lrhip.available, "PolyphaseSynthesizerBlock needs liblrhip.so")
+    self.num_channels = assert(num_channels, "Missing argument #1 (num_channels)")
+    assert(taps, "Missing argument #2 (taps)")
+    if type(taps) == "table" and taps.data_type == nil then
+        self.taps = types.Float32.vector_from_array(taps)
+    else
+        assert(taps.data_type == types.Float32, "Unsupported taps type")
+        self.taps = taps
+    end
+    self.oversample = (options or {}).oversample or 1
+    assert(self.oversample == 1 or self.oversample == 2 or self.oversample == 4, "Unsupported oversample (1, 2 or 4)")
+    self:add_type_signature({block.Input("in", types.ComplexFloat32)}, {block.Output("out", types.ComplexFloat32)})
+end
+
+function PolyphaseSynthesizerBlock:get_rate()
+    return block.Block.get_rate(self) / self.oversample
+end
+
+function PolyphaseSynthesizerBlock:initialize()
+    self.out = types.ComplexFloat32.vector()
+end
+
+-- "pfbsynthesizer:channels=K:oversample=R:taps=v,v,..." (include/lrhip.h)
+function PolyphaseSynthesizerBlock:op()
+    local text = {}
+    for i = 0, self.taps.length - 1 do
+        text[i + 1] = string.format("%.9g", self.taps.data[i].value)
+    end
+    return string.format("pfbsynthesizer:channels=%d:oversample=%d:taps=", self.num_channels, self.oversample) .. table.concat(text, ",")
+end
+
+local M = {PolyphaseChannelizerBlock = PolyphaseChannelizerBlock, PolyphaseSynthesizerBlock = PolyphaseSynthesizerBlock}
 
 -- Does this liblrhip.so have the FFT form?  These files are copied into a LuaRadio checkout and may meet an older library there; LuaJIT raises on the
 -- first index of a symbol the library lacks.  So the entry point is called once, when this file loads, with a shape it refuses before it looks at the
@@ -75,8 +126,9 @@ M.has_oversampled = lrhip.available and pcall(function ()
     return lrhip.lib.lrhip_pfb_oversampled_create(nil, 0, 0, 0)
 end)
 
-function M.patch(Block)
-    lrhip.device_block(Block, function (self)
+-- create: the block's stage constructor; without one, the channelizer's choice among its three entry points
+function M.patch(Block, create)
+    lrhip.device_block(Block, create or function (self)
         local k, m = self.num_channels, self.taps.length
         if self.oversample > 1 then
             assert(M.has_oversampled, "this liblrhip.so has no lrhip_pfb_oversampled_create (oversample = " .. self.oversample .. ")")
@@ -95,5 +147,8 @@ function M.patch(Block)
 end
 
 M.patch(PolyphaseChannelizerBlock)
+M.patch(PolyphaseSynthesizerBlock, function (self)
+    return lrhip.lib.lrhip_unary_create(self:op(), 0, 0, 0, 1)
+end)
 
 return M

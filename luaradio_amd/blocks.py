@@ -374,6 +374,42 @@ class PolyphaseChannelizerBlock(Block):
         return self._execute(x, np.complex64).reshape(-1, self.num_channels)
 
 
+class PolyphaseSynthesizerBlock(Block):
+    """K-channel synthesis filterbank in its polyphase + FFT form, the inverse of PolyphaseChannelizerBlock.  Not a block of the reference: it is
+    K parallel chains UpsamplerBlock(D) -> FIRFilterBlock(taps) -> FrequencyTranslatorBlock(+c*rate_out/K), c = 0 .. K-1, summed, D = K / oversample.
+    PolyphaseSynthesizerBlock(num_channels[, taps[, options]]); default prototype = firwin_lowpass(16*K, 1/K).
+    Input: the frame stream the analysis bank emits, K ComplexFloat32 values per frame (channel c at position c); a call may end inside a frame,
+    whose values wait for the next call.  Output: D samples per completed frame.
+    K a power of two in [8, 4096], K <= len(taps) <= min(64 K, 65536).  options["oversample"] = 2 or 4 (default 1): the frames come at hop D = K / oversample,
+    as those of PolyphaseChannelizerBlock with the same option do; with a matched prototype on both sides the pair reconstructs its input."""
+    name = "PolyphaseSynthesizerBlock"
+
+    def instantiate(self, num_channels, taps=None, options=None):
+        assert num_channels, "Missing argument #1 (num_channels)"
+        self.num_channels = int(num_channels)
+        if taps is None:
+            taps = filter_utils.firwin_lowpass(16 * self.num_channels, 1.0 / self.num_channels)
+        self.taps = types.Float32.vector_from_array(taps)
+        self.oversample = (options or {}).get("oversample", 1)
+        assert self.oversample in (1, 2, 4), "Unsupported oversample \"%s\" (1, 2 or 4)" % (self.oversample,)
+        self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32)])
+
+    def get_rate(self):
+        return Block.get_rate(self) / self.oversample      # K values in per K / oversample samples out
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; %.9g gives every Float32 tap back exactly"""
+        return "pfbsynthesizer:channels=%d:oversample=%d:taps=%s" % (self.num_channels, self.oversample,
+                                                                     ",".join("%.9g" % float(v) for v in np.asarray(self.taps, np.float32)))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 1), "Creating lrhip synthesizer object")
+
+    def process(self, y):
+        """y: an array of shape (frames, K) or the flat frame stream; returns the flat output stream"""
+        return self._execute(np.ascontiguousarray(y).reshape(-1), np.complex64)
+
+
 class _UnaryBlock(Block):
     """One-input element-wise blocks with fixed types."""
     _op, _in, _out = "", types.ComplexFloat32, types.Float32

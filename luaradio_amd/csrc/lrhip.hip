@@ -16,6 +16,7 @@
 #include "kernels_firdecim.h"
 #include "kernels_channelizer.h"
 #include "kernels_pfb.h"
+#include "kernels_pfbsynth.h"
 #include "kernels_iir.h"
 #include "kernels_agc.h"
 #include "kernels_firwin.h"
@@ -68,6 +69,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_preamble.h"
 #include "stage_framers.h"
 #include "stage_modulator.h"
+#include "stage_pfbsynth.h"
 #include "stage_interleave.h"
 #include "stage_source.h"
 #include "chain_plan.h"
@@ -417,6 +419,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         if (head == "preamblesampler") return preamblesampler_create(op);
         // the modulators carry their symbol table as a list (stage_modulator.h)
         if (head == "pam" || head == "qam") return modulator_create(op);
+        // the synthesis filterbank carries its prototype taps the same way (stage_pfbsynth.h)
+        if (head == "pfbsynthesizer") return pfb_synthesizer_create(op);
         // the many-ported stages, whose other side is a port table (stage_interleave.h)
         if (head == "interleave" || head == "deinterleave" || head == "wavpack" || head == "wavunpack") return port_stage_create(op);
         // the generator sources name their waveform / sample type in words and carry a 64-bit seed (stage_source.h)

@@ -194,6 +194,33 @@ def main():
             rows.append({"block": name, "MS/s": round(n / ms_ / 1e3, 1), "bytes_per_sample": bps, "alg_GB/s": round(bps * n / ms_ / 1e6, 1),
                          "frac_8TB/s": round(bps * n / ms_ / 1e6 / 8000, 4), "ms": round(ms_, 4), "ms_runs": [round(v, 4) for v in runs[key]],
                          "bytes_per_s_over_streaming_yardstick": round((bps / ms_) / (16 / stream), 3)})
+    # the synthesis filterbank (kernels_pfbsynth.h): 2^24 frame values in (8 B each) and 2^24 / R samples out per call.  The synthesis block, the analysis
+    # block of the same shape (2^24 samples in, R 2^24 values out) and the streaming yardstick alternate on the same buffers, five runs of 10 calls; the
+    # figure of merit is bytes moved per second over the yardstick's (16 B per sample) in the same runs, every run listed
+    if not only or any(t in "PolyphaseSynthesizer" for t in only):
+        ns = min(n, 1 << 24)
+        mcy = mk(lr.MultiplyConstantBlock, [1.0], True)
+        for k_, m_ in ((64, 1024), (1024, 16384)):
+            taps_ = lr.filter_utils.firwin_lowpass(m_, 1.0 / k_)
+            for r_ in (1, 2, 4):
+                syn = mk(lr.PolyphaseSynthesizerBlock, [k_, taps_, {"oversample": r_}], True)
+                ana = mk(lr.PolyphaseChannelizerBlock, [k_, taps_, {"method": "fft", "oversample": r_}], True)
+                cap_s = max(ana.max_output(ns), syn.max_output(ns), ns)
+                big_s = torch.empty(2 * cap_s + 64, device="cuda")
+                runs = {"syn": [], "ana": [], "stream": []}
+                for _ in range(5):
+                    runs["syn"].append(timeit(lambda: syn.process_device(xc.data_ptr(), ns, big_s.data_ptr(), cap_s), reps=10))
+                    runs["ana"].append(timeit(lambda: ana.process_device(xc.data_ptr(), ns, big_s.data_ptr(), cap_s), reps=10))
+                    runs["stream"].append(timeit(lambda: mcy.process_device(xc.data_ptr(), ns, big_s.data_ptr(), cap_s), reps=10))
+                stream_ms = sorted(runs["stream"])[2]
+                for name, key, bps in (("MultiplyConstant(1.0) cf32 (streaming yardstick, alternating with the synthesizer K=%d R=%d)" % (k_, r_), "stream", 16.0),
+                                       ("PolyphaseChannelizer K=%d, %d taps, oversample=%d (analysis, alternating with the synthesizer)" % (k_, m_, r_), "ana", 8.0 * (1 + r_)),
+                                       ("PolyphaseSynthesizer K=%d, %d taps, oversample=%d (polyphase + FFT, two launches)" % (k_, m_, r_), "syn", 8.0 * (1 + 1.0 / r_))):
+                    ms_ = sorted(runs[key])[2]
+                    rows.append({"block": name, "values_in": ns, "bytes_per_value": bps, "ms": round(ms_, 4), "ms_min": round(min(runs[key]), 4),
+                                 "ms_max": round(max(runs[key]), 4), "ms_runs": [round(v, 4) for v in runs[key]], "alg_GB/s": round(bps * ns / ms_ / 1e6, 1),
+                                 "bytes_per_s_over_streaming_yardstick": round((bps / ms_) / (16 / stream_ms), 3)})
+                del big_s
     if only and not any(t in "WBFM PSD Channelizer" for t in only):
         for r in rows:
             print(json.dumps(r))
