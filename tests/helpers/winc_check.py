@@ -1,7 +1,8 @@
 """Run by tests/test_gpu_firwin.py in a child process with LRHIP_FIR_WIN_CPLX=1 (the knob is read once per process): the
 ComplexFloat32 register-window kernel (kernels_firwin2.h) behind Decimator / Tuner / Tuner + discriminator chains must give the
 bits of the same blocks run one by one (fmaf chains in the reference's tap order, firfilter.lua:266-283; block-of-8 rotator phasors;
-the discriminator's arithmetic), for ragged chunkings including one-sample chunks and odd sample offsets."""
+the discriminator's arithmetic), for ragged chunkings including one-sample chunks and odd sample offsets - with the Hamming lowpass (symmetric
+taps) and with a skewed one (tests/helpers/asym_taps.py), which a window walked backwards does not survive."""
 import os
 import sys
 
@@ -31,12 +32,21 @@ def init(blocks):
     return blocks
 
 
-shapes = {
-    "tuner+disc": lambda: [lr.FrequencyTranslatorBlock(-250e3), lr.LowpassFilterBlock(128, 100e3), lr.DownsamplerBlock(5), lr.FrequencyDiscriminatorBlock(1.25)],
-    "decimator+disc": lambda: [lr.LowpassFilterBlock(128, 100e3), lr.DownsamplerBlock(5), lr.FrequencyDiscriminatorBlock(0.7)],
-    "decimator": lambda: [lr.LowpassFilterBlock(128, 100e3), lr.DownsamplerBlock(5)],
-    "tuner": lambda: [lr.FrequencyTranslatorBlock(123456.0), lr.LowpassFilterBlock(128, 100e3), lr.DownsamplerBlock(5)],
-}
+def chain_shapes(lowpass, tag=""):
+    return {
+        "tuner+disc" + tag: lambda: [lr.FrequencyTranslatorBlock(-250e3), lowpass(), lr.DownsamplerBlock(5), lr.FrequencyDiscriminatorBlock(1.25)],
+        "decimator+disc" + tag: lambda: [lowpass(), lr.DownsamplerBlock(5), lr.FrequencyDiscriminatorBlock(0.7)],
+        "decimator" + tag: lambda: [lowpass(), lr.DownsamplerBlock(5)],
+        "tuner" + tag: lambda: [lr.FrequencyTranslatorBlock(123456.0), lowpass(), lr.DownsamplerBlock(5)],
+    }
+
+
+shapes = chain_shapes(lambda: lr.LowpassFilterBlock(128, 100e3))
+# the same four chains with taps that are not symmetric (tests/helpers/asym_taps.py): a window walked backwards gives other bits than the blocks run one by one
+from tests.helpers import asym_taps as A      # noqa: E402
+skewed = A.skewed_lowpass(128, 100e3 / (rate / 2))
+assert not np.array_equal(skewed, skewed[::-1])
+shapes.update(chain_shapes(lambda: lr.FIRFilterBlock(skewed), ", skewed taps"))
 for name, build in shapes.items():
     ref = init(build())
     want = x
@@ -58,4 +68,9 @@ got = lr.Chain(init(shapes["tuner"]())).process(x)
 assert float(np.max(np.abs(got - ora))) < 2e-6
 dec = lr.Chain(init(shapes["decimator"]())).process(x)
 assert np.array_equal(dec, O.lowpass(128, 100e3, rate, True, mode=O.MODE_FMA).process(x)[::5])
+ora = O.Chain([O.Rotator(2 * np.pi * 123456.0 / rate, O.MODE_F64), O.FIR(skewed, True, O.MODE_FMA)]).process(x)[::5]
+got = lr.Chain(init(shapes["tuner, skewed taps"]())).process(x)
+assert float(np.max(np.abs(got - ora))) < 2e-6
+dec = lr.Chain(init(shapes["decimator, skewed taps"]())).process(x)
+assert np.array_equal(dec, O.FIR(skewed, True, O.MODE_FMA).process(x)[::5])
 print("winc ok")

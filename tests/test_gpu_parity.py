@@ -5,7 +5,9 @@ plus randomized chunkings, large sizes and size-independent properties.
 Tolerances: FIR (real taps) bit-exact vs the oracle's fmaf-chain mode and < 1e-6 vs golden / f64;
 rotator 1e-5 vs golden (reference epsilon) and 1e-6 vs closed form; discriminator 1e-6; downsampler
 bit-exact; IIR 1e-6; DFT 1e-5; PSD 1e-5 (lin) / 3 dB (log, reference epsilon).
-IIR on every kernel form it dispatches (orders, tap counts, launch forms, carry segments, alignment): tests/test_gpu_iir_forms.py."""
+IIR on every kernel form it dispatches (orders, tap counts, launch forms, carry segments, alignment): tests/test_gpu_iir_forms.py.
+The decimating, interpolating and fused real-tap FIR forms with taps that are not symmetric (the lowpass taps used here are, to the bit, so a
+tap index walked backwards passes here): tests/test_gpu_asym_taps.py."""
 import os
 
 import numpy as np

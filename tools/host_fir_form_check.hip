@@ -158,6 +158,39 @@ int main()
         {"bounds: chain tuner50-magnitude", rot(shp(128, 2, 50, 0)), DEF, true, F::DecimLds2, 1, true, true},
         {"bounds: chain tuner50-discriminator", rel(post(rot(shp(128, 2, 50, 0)))), DEF, true, F::DecimLds2, 1, true, false},
         {"bounds: chain audio-tail", iir(shp(136, 1, 5, 54)), DEF, true, F::WinPair, 12800, true, false},
+        // ---- the one-stage shapes of tests/test_gpu_asym_taps.py (tests/helpers/asym_taps.py fir_cases) that no row above pins.  Steps: (4 + 15 D + M) / 4 on a
+        // ComplexFloat32 stream, (6 + 15 D + M) / 4 on a Float32 stream; persistent only at 51 steps (D = 5); no Toeplitz table at D = 9, 12, 18, 25, 50, 75
+        {"asym: MfmaPersistent-f32-m124-d5, 205 / 4 = 51 steps: persistent, not generic", shp(124, 1, 5, 51), DEF, true, F::MfmaPersistent, 1, true, false},
+        {"asym: MfmaGeneric-f32-m122-d5, 203 / 4 = 50 steps", shp(122, 1, 5, 50), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m128-d2", shp(128, 2, 2, 40), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m128-d3", shp(128, 2, 3, 44), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m128-d4", shp(128, 2, 4, 48), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m128-d6", shp(128, 2, 6, 55), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m128-d7", shp(128, 2, 7, 59), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d2", shp(128, 1, 2, 41), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d3", shp(128, 1, 3, 44), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d4", shp(128, 1, 4, 48), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d6", shp(128, 1, 6, 56), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d7", shp(128, 1, 7, 59), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d8", shp(128, 1, 8, 63), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m128-d10", shp(128, 1, 10, 71), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m33-d2", shp(33, 2, 2, 16), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-cf32-m33-d5", shp(33, 2, 5, 28), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m33-d2", shp(33, 1, 2, 17), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: MfmaGeneric-f32-m33-d5", shp(33, 1, 5, 28), DEF, true, F::MfmaGeneric, 1, true, false},
+        {"asym: DecimLds2-cf32-m33-d9", shp(33, 2, 9, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"asym: DecimLds2-cf32-m40-d12", shp(40, 2, 12, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"asym: DecimLds2-cf32-m77-d18", shp(77, 2, 18, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"asym: DecimLds2-cf32-m128-d75", shp(128, 2, 75, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"asym: DecimLds2-cf32-m13-d50", shp(13, 2, 50, 0), DEF, true, F::DecimLds2, 1, true, true},
+        {"asym: DecimLds1-f32-m33-d9", shp(33, 1, 9, 0), DEF, true, F::DecimLds1, 1, true, false},
+        {"asym: DecimLds1-f32-m77-d25", shp(77, 1, 25, 0), DEF, true, F::DecimLds1, 1, true, false},
+        {"asym: DecFft-cf32-m33-d2", decf(shp(33, 2, 2, 16)), DEF, true, F::DecFft, 1, true, false},
+        {"asym: DecFft-cf32-m64-d2", decf(shp(64, 2, 2, 24)), DEF, true, F::DecFft, 1, true, false},
+        {"asym: DecFft-cf32-m128-d5", decf(shp(128, 2, 5, 51)), DEF, true, F::DecFft, 1, true, false},
+        {"asym: DecFft-cf32-m160-d5", decf(shp(160, 2, 5, 59)), DEF, true, F::DecFft, 1, true, false},
+        {"asym: DecFft-cf32-m128-d8", decf(shp(128, 2, 8, 63)), DEF, true, F::DecFft, 1, true, false},
+        {"asym: DecFft-cf32-m256-d8", decf(shp(256, 2, 8, 95)), DEF, true, F::DecFft, 1, true, false},
     };
     const FirShape c1276 = fft(1276, 2, 1280), r1276 = fft(1276, 1, 1280), r768 = fft(768, 1, 768), c2048 = fft(2048, 2, 0, 1);
     const std::vector<FftRow> fft_rows = {
