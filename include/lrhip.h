@@ -139,9 +139,10 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  * "complexconjugate" (ComplexFloat32 in), "realtocomplex", "absolutevalue" (Float32 in), and "addconstant"
  * (radio/blocks/signal/addconstant.lua:26-75: constant (re, im); constant_complex / input_complex as for
  * lrhip_multiply_constant_create).  For the ops with a fixed input type input_complex is ignored.
- * The blocks between a filtered baseband and a bit stream carry double parameters in the op string, "name:key=value:key=value"
- * (values as %.17g / repr(float), parsed with strtod; re / im / constant_complex / input_complex ignored; a malformed string, a missing or
- * unknown key returns NULL with an lrhip_strerror() message).  All exact (compared with ==), state carried across calls:
+ * Every other block created here carries its parameters in the op string, "name:key=value:key=value": the fields in any order, each key once
+ * (luaradio_amd/csrc/op_string.h reads them all; doubles as %.17g / repr(float) text through strtod, integers in decimal, lists of Float32 values
+ * separated by commas; re / im / constant_complex / input_complex ignored; a malformed field, an unknown, repeated or missing key or a value of
+ * the wrong kind returns NULL with an lrhip_strerror() message, before the device is touched).  All exact (compared with ==), state carried across calls:
  *   "zerocrossingclockrecovery:period=P:threshold=T"  (zerocrossingclockrecovery.lua:35-73, P = rate / baudrate) Float32 -> +-1 Float32
  *   "slicer:threshold=T"                               (slicer.lua) Float32 -> Bit (1 B): x > T in double
  *   "differentialdecoder:invert=0|1"                   (differentialdecoder.lua) Bit -> Bit: prev ^ x, or (prev ^ x + 1) % 2; prev = last input byte

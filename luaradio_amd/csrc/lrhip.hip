@@ -3,7 +3,6 @@
 #include "../../include/lrhip.h"
 
 #include <cmath>
-#include <map>
 #include <memory>
 #include <string>
 
@@ -51,6 +50,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
     } while (0)
 
 #include "stage.h"
+#include "op_string.h"
 #include "stage_counted.h"
 #include "stage_fir.h"
 #include "stage_elem.h"
@@ -135,33 +135,30 @@ lrhip_stage_t *lrhip_fir_create(const float *taps, unsigned ntaps, int taps_comp
 lrhip_stage_t *lrhip_rotator_create(double omega)
 {
     if (!std::isfinite(omega)) { set_error("rotator: omega must be finite"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    RotatorStage *q = new (std::nothrow) RotatorStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<RotatorStage>();
+    if (!q) return nullptr;
     q->omega = omega;
     q->step = turns_fixed(omega);
     q->in_size = q->out_size = 8;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_downsampler_create(unsigned factor, int elem_size)
 {
     if (factor < 1) { set_error("downsampler: factor must be >= 1"); return nullptr; }
     if (elem_size != 4 && elem_size != 8) { set_error("downsampler: element size must be 4 or 8"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    DownsamplerStage *q = new (std::nothrow) DownsamplerStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<DownsamplerStage>();
+    if (!q) return nullptr;
     q->factor = factor;
     q->in_size = q->out_size = elem_size;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_fmdiscrim_create(double gain)
 {
     if (!(gain != 0.0) || !std::isfinite(gain)) { set_error("fmdiscrim: gain must be finite and non-zero"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<FmDiscrimStage> q(new (std::nothrow) FmDiscrimStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<FmDiscrimStage>();
+    if (!q) return nullptr;
     q->gain = gain;
     q->in_size = 8; q->out_size = 4;
     if (q->reset()) return nullptr;
@@ -173,82 +170,7 @@ lrhip_stage_t *lrhip_iir_create(const float *b, unsigned nb, const float *a, uns
     if (!b || !a || nb < 1 || na < 1) { set_error("iir: need b_taps and at least one a_tap (iirfilter.lua:56)"); return nullptr; }
     if (nb > IIR_SEQ_MAX || na > IIR_SEQ_MAX) { set_error("iir: at most %d taps supported", IIR_SEQ_MAX); return nullptr; }
     if (a[0] == 0.0f) { set_error("iir: a[0] must be non-zero"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<IirStage> q(new (std::nothrow) IirStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    q->S = input_complex ? 2 : 1;
-    q->in_size = q->out_size = 4 * q->S;
-    q->nb = (int)nb; q->na = (int)na; q->P = (int)na - 1;
-    q->seq.nb = (int)nb; q->seq.na = (int)na;
-    for (unsigned i = 0; i < nb; i++) q->seq.b[i] = b[i];
-    for (unsigned i = 0; i < na; i++) q->seq.a[i] = a[i];
-    q->scan = q->P >= 1 && q->P <= IIR_MAX_P && nb <= IIR_MAX_NB;
-    if (q->scan) {
-        int P = q->P;
-        IirCoeffs &co = q->co;
-        memset(&co, 0, sizeof(co));
-        co.nb = (int)nb; co.P = P;
-        for (unsigned i = 0; i < nb; i++) co.b[i] = (float)((double)b[i] / (double)a[0]);
-        for (int i = 0; i < P; i++) co.a[i] = (float)((double)a[i + 1] / (double)a[0]);
-        // companion matrix of the homogeneous recurrence for the state (y[n-1], ..., y[n-P])
-        std::vector<double> A((size_t)P * P, 0.0), T;
-        for (int k = 0; k < P; k++) A[k] = -(double)co.a[k];
-        for (int r = 1; r < P; r++) A[r * P + r - 1] = 1.0;
-        T = A;
-        for (int s = 1; s < IIR_LC; s <<= 1) matmul(T, T, T, P);      // A^LC (LC is a power of two)
-        std::vector<float> tpow((size_t)9 * P * P);
-        std::vector<double> tpow64((size_t)9 * P * P);
-        const double p16 = P == 1 ? T[0] : 0.0;                     // first order: A^LC is the scalar p^16
-        for (int k = 0; k <= 8; k++) {
-            for (int i = 0; i < P * P; i++) { tpow[(size_t)k * P * P + i] = (float)T[i]; tpow64[(size_t)k * P * P + i] = T[i]; }
-            if (k == 8) q->Ttile = T;
-            matmul(T, T, T, P);
-        }
-        if (P == 1 && std::fabs(p16) < 1.0 && p16 != 0.0) {
-            // chunks of 16 samples after which a zero start has decayed to 1e-12: the partial warm-up of the one-shot launch
-            const int wc = (int)std::ceil(std::log(1e-12) / std::log(std::fabs(p16)));
-            if (wc >= 1 && wc <= 128) q->warm_chunks = wc;
-        } else if (P == 1 && p16 == 0.0) {
-            q->warm_chunks = 1;
-        }
-        // (orders 2-4 were given the same one-shot launch in round 3 - 4 chunks of warm-up instead of a whole tile per 8 - and lost: 0.417 against 0.372 ms
-        // for the suite's 3-feedback-tap entry on ComplexFloat32, same box: every workgroup then runs the 18-barrier block scan twice per emitted tile)
-        // Round 3, on top of the two-barrier wave scan: a workgroup per tile still loses (0.267 against 0.232 ms), but the partial warm-up tile itself pays
-        // at the old 8 tiles per workgroup - 0.213 (stage_iir.h has the table).
-        if (P >= 2 && P <= 4) {
-            std::vector<double> A16(tpow64.begin(), tpow64.begin() + P * P), M = A16;
-            for (int wc = 1; wc <= 128 && !q->warm_chunks; wc++) {
-                double mx = 0.0;
-                for (double v : M) mx = std::fabs(v) > mx ? std::fabs(v) : mx;
-                if (std::isfinite(mx) && mx < 1e-12) q->warm_chunks = wc;
-                matmul(M, A16, M, P);
-            }
-        }
-        if (P == 1) {                                               // p^(16 (l + 1)), l < 64: the per-lane powers of the single-launch kernel's wave scan
-            double acc = 1.0;
-            for (int l = 0; l < 64; l++) { acc *= p16; tpow.push_back((float)acc); }
-        } else if (P <= 4) {                                        // the same for orders 2-4: the matrices A^(16 (l + 1))
-            std::vector<double> A16(tpow64.begin(), tpow64.begin() + P * P), M = A16;
-            for (int l = 0; l < 64; l++) {
-                for (int i = 0; i < P * P; i++) tpow.push_back((float)M[i]);
-                matmul(M, A16, M, P);
-            }
-        }
-        if (P > 4 ? upload(q->d_tpow, tpow64.data(), tpow64.size() * sizeof(double)) : upload(q->d_tpow, tpow.data(), tpow.size() * sizeof(float))) return nullptr;
-        if (upload(q->d_ttile, q->Ttile.data(), q->Ttile.size() * sizeof(double))) return nullptr;
-        // memory shorter than `w` tiles in Float32 terms?  (every entry of A^(w*TILE) underflows)  -> single-launch kernel
-        static const bool force_3pass = getenv("LRHIP_IIR_3PASS") != nullptr;       // A/B knob
-        std::vector<double> W = q->Ttile;
-        for (int w = 1; w <= 4 && !force_3pass && !q->warm_tiles; w *= 2) {
-            double mx = 0.0;
-            bool finite = true;
-            for (double v : W) { finite = finite && std::isfinite(v); mx = std::fabs(v) > mx ? std::fabs(v) : mx; }
-            if (finite && mx < 1e-46) q->warm_tiles = w;
-            matmul(W, W, W, P);
-        }
-    }
-    if (q->reset()) return nullptr;
-    return q.release();
+    return iir_build(b, nb, a, na, input_complex);
 }
 
 lrhip_stage_t *lrhip_psd_create(unsigned n, const float *window, double scale, int logarithmic, int input_complex, int fftshift)
@@ -329,14 +251,13 @@ lrhip_stage_t *lrhip_format_convert_create(const char *format, int complex_out)
     for (size_t i = 0; i < sizeof(kFormats) / sizeof(kFormats[0]); i++)
         if (!strcmp(kFormats[i].name, format)) idx = (int)i;
     if (idx < 0) { set_error("Unsupported format (\"%s\")", format); return nullptr; }     // iqfile.lua:48
-    if (ensure_init()) return nullptr;
-    FormatStage *q = new (std::nothrow) FormatStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<FormatStage>();
+    if (!q) return nullptr;
     q->fmt = idx;
     q->scalars = complex_out ? 2 : 1;
     q->in_size = kFormats[idx].bytes * q->scalars;
     q->out_size = 4 * q->scalars;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_format_pack_create(const char *format, int complex_in)
@@ -351,34 +272,31 @@ lrhip_stage_t *lrhip_format_pack_create(const char *format, int complex_in)
 lrhip_stage_t *lrhip_multiply_constant_create(float re, float im, int constant_complex, int input_complex)
 {
     if (constant_complex && !input_complex) { set_error("multiplyconstant: a complex constant takes ComplexFloat32 input only (multiplyconstant.lua:42-44)"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    MulConstStage *q = new (std::nothrow) MulConstStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<MulConstStage>();
+    if (!q) return nullptr;
     q->cr = re; q->ci = constant_complex ? im : 0.f;
     q->mode = !input_complex ? 0 : (constant_complex ? 2 : 1);
     q->in_size = q->out_size = input_complex ? 8 : 4;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_upsampler_create(unsigned factor, int elem_size)
 {
     if (factor < 1) { set_error("upsampler: factor must be >= 1"); return nullptr; }
     if (elem_size != 4 && elem_size != 8) { set_error("upsampler: element size must be 4 or 8"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    UpsamplerStage *q = new (std::nothrow) UpsamplerStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<UpsamplerStage>();
+    if (!q) return nullptr;
     q->factor = factor;
     q->in_size = q->out_size = elem_size;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_agc_create(double power_alpha, double gain_alpha, double target, double threshold, int input_complex)
 {
     if (!(power_alpha > 0.0 && power_alpha <= 1.0) || !(gain_alpha > 0.0 && gain_alpha <= 1.0)) { set_error("agc: alphas must be in (0, 1]"); return nullptr; }
     if (!(target > 0.0) || !(threshold >= 0.0)) { set_error("agc: target and threshold are linear powers (> 0)"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<AgcStage> q(new (std::nothrow) AgcStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<AgcStage>();
+    if (!q) return nullptr;
     q->p = AgcParams{power_alpha, gain_alpha, target, threshold};
     q->S = input_complex ? 2 : 1;
     q->in_size = q->out_size = 4 * q->S;
@@ -397,9 +315,8 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
 lrhip_stage_t *lrhip_fmmod_create(double modulation_index)
 {
     if (!std::isfinite(modulation_index)) { set_error("fmmod: modulation index must be finite"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<FmModStage> q(new (std::nothrow) FmModStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<FmModStage>();
+    if (!q) return nullptr;
     q->k = modulation_index;
     q->in_size = 4; q->out_size = 8;
     if (q->reset()) return nullptr;
@@ -409,43 +326,19 @@ lrhip_stage_t *lrhip_fmmod_create(double modulation_index)
 lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int constant_complex, int input_complex)
 {
     if (!op) { set_error("unary: missing operation name"); return nullptr; }
-    {
-        // the digital blocks carry double parameters in the op string (stage_digital.h)
-        std::string name;
-        std::map<std::string, double> kv;
-        const char *c = strchr(op, ':');
-        const std::string head(op, c ? (size_t)(c - op) : strlen(op));
-        // the preamble travels as a string of 0 / 1 characters, which strtod would not keep (stage_preamble.h)
-        if (head == "preamblesampler") return preamblesampler_create(op);
-        // the modulators carry their symbol table as a list (stage_modulator.h)
-        if (head == "pam" || head == "qam") return modulator_create(op);
-        // the synthesis filterbank carries its prototype taps the same way (stage_pfbsynth.h)
-        if (head == "pfbsynthesizer") return pfb_synthesizer_create(op);
-        // the many-ported stages, whose other side is a port table (stage_interleave.h)
-        if (head == "interleave" || head == "deinterleave" || head == "wavpack" || head == "wavunpack") return port_stage_create(op);
-        // the generator sources name their waveform / sample type in words and carry a 64-bit seed (stage_source.h)
-        if (head == "signalsource" || head == "uniformrandomsource") return source_create(op);
-        // the PLL names its output port in words (stage_pll.h)
-        if (head == "pll") return pll_create(op);
-        // the five framers take no parameters at all (stage_framers.h)
-        if (head == "rdsframer") return plain_create<RfStage>(op, 8);
-        if (head == "scmframer") return plain_create<EfStage<EF_SCM>>(op, EfProto<EF_SCM>::REC);
-        if (head == "scmplusframer") return plain_create<EfStage<EF_SCMPLUS>>(op, EfProto<EF_SCMPLUS>::REC);
-        if (head == "idmframer") return plain_create<EfStage<EF_IDM>>(op, EfProto<EF_IDM>::REC);
-        if (head == "ax25framer") return plain_create<AxStage>(op, AX_REC);
-        if (head == "pocsagframer") return plain_create<PgStage>(op, PG_REC);
-        // nor does the Varicode decoder (stage_preamble.h)
-        if (head == "varicodedecoder") return plain_create<VcStage>(op, 1);
-        if (head == "manchesterdecoder") {
-            if (!parse_op(op, name, kv, {"invert"})) return nullptr;
-            return manchesterdecoder_create(kv, op);
-        }
-        if (c || digital_unary_op(head)) {
-            if (!digital_unary_op(head)) { set_error("unary: unknown operation \"%s\"", op); return nullptr; }
-            if (!parse_op(op, name, kv, digital_keys(head))) return nullptr;
-            return digital_unary_create(name, kv, op);
-        }
-    }
+    // the stages that read an op string "name:key=value:..." (op_string.h), and the parameterless ones (plain_create, stage_counted.h)
+    static const struct { const char *head; lrhip_stage_t *(*create)(const char *op); } kCreators[] = {
+        {"zerocrossingclockrecovery", zc_create}, {"clocksampler", zc_create}, {"slicer", slicer_create}, {"differentialdecoder", diffdec_create},
+        {"binaryphasecorrector", phasecorr_create}, {"pll", pll_create}, {"preamblesampler", preamblesampler_create},
+        {"manchesterdecoder", manchesterdecoder_create}, {"pam", modulator_create}, {"qam", modulator_create},
+        {"pfbsynthesizer", pfb_synthesizer_create}, {"interleave", port_stage_create}, {"deinterleave", port_stage_create},
+        {"wavpack", port_stage_create}, {"wavunpack", port_stage_create}, {"signalsource", source_create}, {"uniformrandomsource", source_create},
+        {"rdsframer", plain_create<RfStage, 8>}, {"scmframer", plain_create<EfStage<EF_SCM>, EfProto<EF_SCM>::REC>},
+        {"scmplusframer", plain_create<EfStage<EF_SCMPLUS>, EfProto<EF_SCMPLUS>::REC>}, {"idmframer", plain_create<EfStage<EF_IDM>, EfProto<EF_IDM>::REC>},
+        {"ax25framer", plain_create<AxStage, AX_REC>}, {"pocsagframer", plain_create<PgStage, PG_REC>}, {"varicodedecoder", plain_create<VcStage, 1>}};
+    const size_t head_len = strcspn(op, ":");
+    for (auto &c : kCreators)
+        if (strlen(c.head) == head_len && !strncmp(c.head, op, head_len)) return c.create(op);
     struct { const char *name; int code, in, out; } T[] = {
         {"complexmagnitude", UN_CMAG, 8, 4}, {"complexphase", UN_CPHASE, 8, 4}, {"complextoreal", UN_CREAL, 8, 4},
         {"complextoimag", UN_CIMAG, 8, 4},   {"complexconjugate", UN_CCONJ, 8, 8}, {"realtocomplex", UN_R2C, 4, 8},
@@ -459,21 +352,19 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         in = out = input_complex ? 8 : 4;
     }
     if (code < 0) { set_error("unary: unknown operation \"%s\"", op); return nullptr; }
-    if (ensure_init()) return nullptr;
-    UnaryStage *q = new (std::nothrow) UnaryStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<UnaryStage>();
+    if (!q) return nullptr;
     q->op = code; q->cr = re; q->ci = im;
     q->in_size = in; q->out_size = out;
-    return q;
+    return q.release();
 }
 
 lrhip_stage_t *lrhip_delay_create(unsigned num_samples, int elem_size)
 {
     if (num_samples < 1) { set_error("Number of samples must be greater than 0"); return nullptr; }      // delay.lua:28
     if (elem_size != 4 && elem_size != 8) { set_error("delay: element size must be 4 or 8"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<DelayStage> q(new (std::nothrow) DelayStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<DelayStage>();
+    if (!q) return nullptr;
     q->D = num_samples;
     q->in_size = q->out_size = elem_size;
     if (q->reset()) return nullptr;
@@ -495,29 +386,7 @@ lrhip_stage_t *lrhip_channelizer_create(const float *taps, unsigned ntaps, unsig
 {
     if (!taps || ntaps < 32 || (ntaps % 32) != 0 || ntaps > 8192) { set_error("channelizer: ntaps must be a multiple of 32 in [32, 8192]"); return nullptr; }
     if (nchannels != 32 && nchannels != 64) { set_error("channelizer: nchannels must be 32 or 64"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<ChannelizerStage> q(new (std::nothrow) ChannelizerStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    int M = (int)ntaps, K = (int)nchannels, K2 = 2 * K;
-    q->M = M; q->K = K;
-    q->in_size = q->out_size = 8;
-    // W[2i][2c] = Re g, W[2i+1][2c] = -Im g, W[2i][2c+1] = Im g, W[2i+1][2c+1] = Re g,
-    // g_c[i] = h[M-1-i] * exp(+j*2*pi*c*(M-1-i)/K)   (kernels_channelizer.h)
-    std::vector<float> W((size_t)2 * M * K2);
-    const double PI2 = 6.283185307179586476925286766559;
-    for (int i = 0; i < M; i++)
-        for (int c = 0; c < K; c++) {
-            int j = M - 1 - i;
-            double a = PI2 * (double)(((long)c * j) % K) / K, h = taps[j];
-            float gr = (float)(h * std::cos(a)), gi = (float)(h * std::sin(a));
-            W[(size_t)(2 * i) * K2 + 2 * c] = gr;
-            W[(size_t)(2 * i + 1) * K2 + 2 * c] = -gi;
-            W[(size_t)(2 * i) * K2 + 2 * c + 1] = gi;
-            W[(size_t)(2 * i + 1) * K2 + 2 * c + 1] = gr;
-        }
-    if (upload(q->W, W.data(), W.size() * sizeof(float))) return nullptr;
-    if (q->reset()) return nullptr;
-    return q.release();
+    return channelizer_build(taps, ntaps, nchannels);
 }
 
 lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, unsigned nchannels)
@@ -528,9 +397,8 @@ lrhip_stage_t *lrhip_pfb_channelizer_create(const float *taps, unsigned ntaps, u
 lrhip_stage_t *lrhip_pfb_oversampled_create(const float *taps, unsigned ntaps, unsigned nchannels, unsigned oversample)
 {
     if (const char *why = PfbChannelizerStage::refusal(taps ? ntaps : 0, nchannels, oversample)) { set_error("%s", why); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PfbChannelizerStage> q(new (std::nothrow) PfbChannelizerStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<PfbChannelizerStage>();
+    if (!q) return nullptr;
     const int M = (int)ntaps, K = (int)nchannels;
     q->M = M; q->K = K; q->P = (M + K - 1) / K;
     q->R = (int)oversample; q->D = K / q->R;
@@ -552,9 +420,8 @@ lrhip_stage_t *lrhip_binary_create(const char *op, int input_complex)
     if (!op) { set_error("binary: missing operation name"); return nullptr; }
     if (!strcmp(op, "sampler")) {
         // SamplerBlock: data (ComplexFloat32 / Float32, input_complex) and a Float32 clock; the output count depends on the clock
-        if (ensure_init()) return nullptr;
-        std::unique_ptr<SamplerStage> q(new (std::nothrow) SamplerStage());
-        if (!q) { set_error("out of memory"); return nullptr; }
+        auto q = new_stage<SamplerStage>();
+        if (!q) return nullptr;
         q->in_size = q->out_size = input_complex ? 8 : 4;
         q->in2_size = 4;
         if (q->reset()) return nullptr;
@@ -564,13 +431,12 @@ lrhip_stage_t *lrhip_binary_create(const char *op, int input_complex)
              : !strcmp(op, "add") ? BIN_ADD : !strcmp(op, "subtract") ? BIN_SUBTRACT : !strcmp(op, "floattocomplex") ? BIN_F2C : -1;
     if (code < 0) { set_error("binary: unknown operation \"%s\"", op); return nullptr; }
     if (code == BIN_MULTIPLY_CONJ && !input_complex) { set_error("binary: multiplyconjugate takes ComplexFloat32 inputs (multiplyconjugate.lua:26)"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    BinaryStage *q = new (std::nothrow) BinaryStage();
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<BinaryStage>();
+    if (!q) return nullptr;
     q->op = code;
     q->in_size = q->out_size = input_complex ? 8 : 4;
     if (code == BIN_F2C) { q->in_size = 4; q->out_size = 8; }
-    return q;
+    return q.release();
 }
 
 void lrhip_stage_destroy(lrhip_stage_t *q)

@@ -40,6 +40,15 @@ struct lrhip_stage {
     virtual void rate(unsigned long *num, unsigned long *den) const { *num = 1; *den = 1; }
 };
 
+// the device initialised, then an S: null with the message set.  Every creator calls it AFTER its parameter checks, which need no device.
+template <class S> static std::unique_ptr<S> new_stage()
+{
+    if (ensure_init()) return nullptr;
+    std::unique_ptr<S> q(new (std::nothrow) S());
+    if (!q) set_error("out of memory");
+    return q;
+}
+
 static int upload(DeviceBuf &b, const void *src, size_t bytes)
 {
     if (b.reserve(bytes ? bytes : 4)) return -1;

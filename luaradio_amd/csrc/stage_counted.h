@@ -108,14 +108,13 @@ struct SamplerScratch : Carve {
 };
 
 // ---- a stage that takes no parameters: Bit in, records of out_size bytes out
-template <class Stage> static lrhip_stage_t *plain_create(const char *op, int out_size)
+template <class Stage, int OUT_SIZE> static lrhip_stage_t *plain_create(const char *op)
 {
     // (lrhip_unary_create has matched the op's name, the text in front of the ':', to the stage)
     if (const char *c = strchr(op, ':')) { set_error("%.*s: takes no parameters, got \"%s\"", (int)(c - op), op, op); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<Stage> q(new (std::nothrow) Stage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    q->in_size = 1; q->out_size = out_size;
+    auto q = new_stage<Stage>();
+    if (!q) return nullptr;
+    q->in_size = 1; q->out_size = OUT_SIZE;
     if (q->reset()) return nullptr;
     return q.release();
 }

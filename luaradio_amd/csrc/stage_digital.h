@@ -4,31 +4,6 @@
 // (part of liblrhip.so; included by lrhip.hip after stage_elem2.h, one translation unit)
 #pragma once
 
-// "name:key=value:key=value" -> name and a key -> double map; values through strtod (exact for %.17g / repr() text).  false + lrhip_strerror
-// on a malformed string or a key outside `allowed`.
-static bool parse_op(const char *op, std::string &name, std::map<std::string, double> &kv, std::initializer_list<const char *> allowed)
-{
-    const char *c = strchr(op, ':');
-    name.assign(op, c ? (size_t)(c - op) : strlen(op));
-    while (c) {
-        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
-        if (!eq || (next && eq > next) || eq == k) { set_error("%s: malformed parameter in \"%s\" (expected key=value)", name.c_str(), op); return false; }
-        const std::string key(k, (size_t)(eq - k));
-        bool ok = false;
-        for (const char *a : allowed) ok = ok || key == a;
-        if (!ok) { set_error("%s: unknown parameter \"%s\"", name.c_str(), key.c_str()); return false; }
-        const char *v = eq + 1, *vend = next ? next : v + strlen(v);
-        char *end = nullptr;
-        errno = 0;
-        const double d = strtod(v, &end);
-        if (v == vend || end != vend || errno == ERANGE) { set_error("%s: bad value for \"%s\" in \"%s\"", name.c_str(), key.c_str(), op); return false; }
-        if (kv.count(key)) { set_error("%s: parameter \"%s\" given twice", name.c_str(), key.c_str()); return false; }
-        kv[key] = d;
-        c = next;
-    }
-    return true;
-}
-
 // The clock recovery's closed form (kernels_digital.h) for symbol period P: decided here, and only where it is proven.
 //   P >= 2, 2^e <= P < 2^(e+1) with P + 1 <= 2^(e+1), and P < 2^40.
 //   From each kind of reset the literal loop runs (exactly: an offset >= 1 loses integers without rounding) to its first pulse ks, whose add gives
@@ -225,61 +200,47 @@ struct DiffDecStage : lrhip_stage {
     }
 };
 
-// ---- constructors behind lrhip_unary_create / lrhip_binary_create (op strings "name:key=value...")
-static lrhip_stage_t *digital_unary_create(const std::string &name, const std::map<std::string, double> &kv, const char *op)
+// ---- constructors behind lrhip_unary_create (op strings, op_string.h)
+// "zerocrossingclockrecovery:period=P:threshold=T" and "clocksampler:period=P:threshold=T"
+static lrhip_stage_t *zc_create(const char *op)
 {
-    auto need = [&](const char *k, double &v) {
-        auto it = kv.find(k);
-        if (it == kv.end()) { set_error("%s: missing parameter \"%s\" in \"%s\"", name.c_str(), k, op); return false; }
-        v = it->second;
-        return true;
-    };
-    double P = 0.0, T = 0.0, inv = 0.0;
-    if (name == "binaryphasecorrector") return phasecorr_create(kv, op);
-    if (name == "zerocrossingclockrecovery" || name == "clocksampler") {
-        if (!need("period", P) || !need("threshold", T)) return nullptr;
-        if (!(P > 0.0) || !std::isfinite(P)) { set_error("%s: period must be finite and > 0", name.c_str()); return nullptr; }
-        if (!std::isfinite(T)) { set_error("%s: threshold must be finite", name.c_str()); return nullptr; }
-        if (ensure_init()) return nullptr;
-        std::unique_ptr<ZcStage> q(new (std::nothrow) ZcStage());
-        if (!q) { set_error("out of memory"); return nullptr; }
-        zc_prepare(P, T, q->p);
-        q->sampler = name == "clocksampler";
-        q->in_size = q->out_size = 4;
-        if (q->reset()) return nullptr;
-        return q.release();
-    }
-    if (name == "slicer") {
-        if (!need("threshold", T)) return nullptr;
-        if (ensure_init()) return nullptr;
-        std::unique_ptr<SlicerStage> q(new (std::nothrow) SlicerStage());
-        if (!q) { set_error("out of memory"); return nullptr; }
-        q->t = T;
-        q->in_size = 4; q->out_size = 1;
-        return q.release();
-    }
-    if (name == "differentialdecoder") {
-        if (!need("invert", inv)) return nullptr;
-        if (inv != 0.0 && inv != 1.0) { set_error("differentialdecoder: invert must be 0 or 1"); return nullptr; }
-        if (ensure_init()) return nullptr;
-        std::unique_ptr<DiffDecStage> q(new (std::nothrow) DiffDecStage());
-        if (!q) { set_error("out of memory"); return nullptr; }
-        q->invert = inv != 0.0;
-        q->in_size = q->out_size = 1;
-        if (q->reset()) return nullptr;
-        return q.release();
-    }
-    return nullptr;
+    OpFields f;
+    double P = 0.0, T = 0.0;
+    if (!f.split(op, nullptr, {{"period", nullptr}, {"threshold", nullptr}}, true) || !f.number("period", P) || !f.number("threshold", T)) return nullptr;
+    if (!(P > 0.0) || !std::isfinite(P)) { set_error("%s: period must be finite and > 0", f.name.c_str()); return nullptr; }
+    if (!std::isfinite(T)) { set_error("%s: threshold must be finite", f.name.c_str()); return nullptr; }
+    auto q = new_stage<ZcStage>();
+    if (!q) return nullptr;
+    zc_prepare(P, T, q->p);
+    q->sampler = f.name == "clocksampler";
+    q->in_size = q->out_size = 4;
+    if (q->reset()) return nullptr;
+    return q.release();
 }
-// the keys each op takes (anything else is refused)
-static std::initializer_list<const char *> digital_keys(const std::string &name)
+
+// "slicer:threshold=T"
+static lrhip_stage_t *slicer_create(const char *op)
 {
-    static const std::initializer_list<const char *> zc = {"period", "threshold"}, sl = {"threshold"}, dd = {"invert"},
-                                                     pc = {"num_samples", "sample_interval"};
-    return name == "slicer" ? sl : name == "differentialdecoder" ? dd : name == "binaryphasecorrector" ? pc : zc;
+    OpFields f;
+    double T = 0.0;
+    if (!f.split(op, "slicer", {{"threshold", nullptr}}, true) || !f.number("threshold", T)) return nullptr;
+    auto q = new_stage<SlicerStage>();
+    if (!q) return nullptr;
+    q->t = T;
+    q->in_size = 4; q->out_size = 1;
+    return q.release();
 }
-static bool digital_unary_op(const std::string &name)
+
+// "differentialdecoder:invert=0|1"
+static lrhip_stage_t *diffdec_create(const char *op)
 {
-    return name == "zerocrossingclockrecovery" || name == "clocksampler" || name == "slicer" || name == "differentialdecoder" ||
-           name == "binaryphasecorrector";
+    OpFields f;
+    bool invert = false;
+    if (!f.split(op, "differentialdecoder", {{"invert", nullptr}}, true) || !f.flag("invert", invert)) return nullptr;
+    auto q = new_stage<DiffDecStage>();
+    if (!q) return nullptr;
+    q->invert = invert;
+    q->in_size = q->out_size = 1;
+    if (q->reset()) return nullptr;
+    return q.release();
 }

@@ -104,9 +104,8 @@ struct FirWinRealStage : lrhip_stage {
 static FirWinRealStage *firwin_real_build(const float *taps, int M, const float *b, int nb, const float *a, int na, unsigned long D)
 {
     if (!FirWinRealStage::supported_taps(M)) { set_error("firwin: no instantiation for %d taps", M); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<FirWinRealStage> q(new (std::nothrow) FirWinRealStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<FirWinRealStage>();
+    if (!q) return nullptr;
     q->M = M; q->D = D;
     q->in_size = q->out_size = 4;
     q->taps_rev.resize((size_t)M);

@@ -137,6 +137,87 @@ struct IirStage : lrhip_stage {
     }
 };
 
+// The stage behind lrhip_iir_create, which has checked the taps: the sequential form's coefficients and, for the scan forms (orders 1 .. IIR_MAX_P),
+// the normalised coefficients and the powers of the recurrence's companion matrix that the kernels step by.
+static IirStage *iir_build(const float *b, unsigned nb, const float *a, unsigned na, int input_complex)
+{
+    auto q = new_stage<IirStage>();
+    if (!q) return nullptr;
+    q->S = input_complex ? 2 : 1;
+    q->in_size = q->out_size = 4 * q->S;
+    q->nb = (int)nb; q->na = (int)na; q->P = (int)na - 1;
+    q->seq.nb = (int)nb; q->seq.na = (int)na;
+    for (unsigned i = 0; i < nb; i++) q->seq.b[i] = b[i];
+    for (unsigned i = 0; i < na; i++) q->seq.a[i] = a[i];
+    q->scan = q->P >= 1 && q->P <= IIR_MAX_P && nb <= IIR_MAX_NB;
+    if (q->scan) {
+        int P = q->P;
+        IirCoeffs &co = q->co;
+        memset(&co, 0, sizeof(co));
+        co.nb = (int)nb; co.P = P;
+        for (unsigned i = 0; i < nb; i++) co.b[i] = (float)((double)b[i] / (double)a[0]);
+        for (int i = 0; i < P; i++) co.a[i] = (float)((double)a[i + 1] / (double)a[0]);
+        // companion matrix of the homogeneous recurrence for the state (y[n-1], ..., y[n-P])
+        std::vector<double> A((size_t)P * P, 0.0), T;
+        for (int k = 0; k < P; k++) A[k] = -(double)co.a[k];
+        for (int r = 1; r < P; r++) A[r * P + r - 1] = 1.0;
+        T = A;
+        for (int s = 1; s < IIR_LC; s <<= 1) matmul(T, T, T, P);      // A^LC (LC is a power of two)
+        std::vector<float> tpow((size_t)9 * P * P);
+        std::vector<double> tpow64((size_t)9 * P * P);
+        const double p16 = P == 1 ? T[0] : 0.0;                     // first order: A^LC is the scalar p^16
+        for (int k = 0; k <= 8; k++) {
+            for (int i = 0; i < P * P; i++) { tpow[(size_t)k * P * P + i] = (float)T[i]; tpow64[(size_t)k * P * P + i] = T[i]; }
+            if (k == 8) q->Ttile = T;
+            matmul(T, T, T, P);
+        }
+        if (P == 1 && std::fabs(p16) < 1.0 && p16 != 0.0) {
+            // chunks of 16 samples after which a zero start has decayed to 1e-12: the partial warm-up of the one-shot launch
+            const int wc = (int)std::ceil(std::log(1e-12) / std::log(std::fabs(p16)));
+            if (wc >= 1 && wc <= 128) q->warm_chunks = wc;
+        } else if (P == 1 && p16 == 0.0) {
+            q->warm_chunks = 1;
+        }
+        // (orders 2-4 were given the same one-shot launch in round 3 - 4 chunks of warm-up instead of a whole tile per 8 - and lost: 0.417 against 0.372 ms
+        // for the suite's 3-feedback-tap entry on ComplexFloat32, same box: every workgroup then runs the 18-barrier block scan twice per emitted tile)
+        // Round 3, on top of the two-barrier wave scan: a workgroup per tile still loses (0.267 against 0.232 ms), but the partial warm-up tile itself pays
+        // at the old 8 tiles per workgroup - 0.213 (run_scan_nb above has the table).
+        if (P >= 2 && P <= 4) {
+            std::vector<double> A16(tpow64.begin(), tpow64.begin() + P * P), M = A16;
+            for (int wc = 1; wc <= 128 && !q->warm_chunks; wc++) {
+                double mx = 0.0;
+                for (double v : M) mx = std::fabs(v) > mx ? std::fabs(v) : mx;
+                if (std::isfinite(mx) && mx < 1e-12) q->warm_chunks = wc;
+                matmul(M, A16, M, P);
+            }
+        }
+        if (P == 1) {                                               // p^(16 (l + 1)), l < 64: the per-lane powers of the single-launch kernel's wave scan
+            double acc = 1.0;
+            for (int l = 0; l < 64; l++) { acc *= p16; tpow.push_back((float)acc); }
+        } else if (P <= 4) {                                        // the same for orders 2-4: the matrices A^(16 (l + 1))
+            std::vector<double> A16(tpow64.begin(), tpow64.begin() + P * P), M = A16;
+            for (int l = 0; l < 64; l++) {
+                for (int i = 0; i < P * P; i++) tpow.push_back((float)M[i]);
+                matmul(M, A16, M, P);
+            }
+        }
+        if (P > 4 ? upload(q->d_tpow, tpow64.data(), tpow64.size() * sizeof(double)) : upload(q->d_tpow, tpow.data(), tpow.size() * sizeof(float))) return nullptr;
+        if (upload(q->d_ttile, q->Ttile.data(), q->Ttile.size() * sizeof(double))) return nullptr;
+        // memory shorter than `w` tiles in Float32 terms?  (every entry of A^(w*TILE) underflows)  -> single-launch kernel
+        static const bool force_3pass = getenv("LRHIP_IIR_3PASS") != nullptr;       // A/B knob
+        std::vector<double> W = q->Ttile;
+        for (int w = 1; w <= 4 && !force_3pass && !q->warm_tiles; w *= 2) {
+            double mx = 0.0;
+            bool finite = true;
+            for (double v : W) { finite = finite && std::isfinite(v); mx = std::fabs(v) > mx ? std::fabs(v) : mx; }
+            if (finite && mx < 1e-46) q->warm_tiles = w;
+            matmul(W, W, W, P);
+        }
+    }
+    if (q->reset()) return nullptr;
+    return q.release();
+}
+
 // =====================================================================================================
 // AGCBlock
 // =====================================================================================================

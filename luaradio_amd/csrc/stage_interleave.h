@@ -112,26 +112,21 @@ struct PortStage : lrhip_stage {
 
 static lrhip_stage_t *port_stage_create(const char *op)
 {
-    std::string name;
-    std::map<std::string, double> kv;
-    const char *c = strchr(op, ':');
-    const std::string head(op, c ? (size_t)(c - op) : strlen(op));
-    const bool wav = head == "wavpack" || head == "wavunpack";
+    OpFields f;
+    const bool wav = !strncmp(op, "wav", 3);
     const char *second = wav ? "bits" : "size";
-    if (!parse_op(op, name, kv, {"channels", second})) return nullptr;
-    for (const char *key : {"channels", second})
-        if (!kv.count(key)) { set_error("%s: missing parameter \"%s\"", name.c_str(), key); return nullptr; }
-    const double ch = kv["channels"], sz = kv[second];
+    double ch = 0.0, sz = 0.0;
+    if (!f.split(op, nullptr, {{"channels", nullptr}, {second, nullptr}}, true) || !f.number("channels", ch) || !f.number(second, sz)) return nullptr;
+    const std::string &name = f.name;
     const int lo = wav ? 1 : 2;
     if (!(ch >= lo && ch <= IL_MAX_CH) || ch != std::floor(ch)) { set_error("%s: channels must be an integer in %d .. %d (got %g)", name.c_str(), lo, IL_MAX_CH, ch); return nullptr; }
     if (wav ? (sz != 8 && sz != 16 && sz != 32) : (sz != 4 && sz != 8)) {
         set_error(wav ? "%s: bits must be 8, 16 or 32 (got %g)" : "%s: size must be 4 or 8 (got %g)", name.c_str(), sz);
         return nullptr;
     }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PortStage> q(new (std::nothrow) PortStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    q->what = head == "interleave" ? PortStage::INTERLEAVE : head == "deinterleave" ? PortStage::DEINTERLEAVE : head == "wavpack" ? PortStage::WAVPACK : PortStage::WAVUNPACK;
+    auto q = new_stage<PortStage>();
+    if (!q) return nullptr;
+    q->what = name == "interleave" ? PortStage::INTERLEAVE : name == "deinterleave" ? PortStage::DEINTERLEAVE : name == "wavpack" ? PortStage::WAVPACK : PortStage::WAVUNPACK;
     q->N = (unsigned)ch;
     if (!wav) {
         q->form = sz == 8 ? IL_COPY8 : IL_COPY4;

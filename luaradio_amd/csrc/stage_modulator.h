@@ -64,9 +64,8 @@ struct ModStage : lrhip_stage {
 
 static ModStage *modulator_build(bool qam, unsigned P, int b, int msb, const std::vector<float> &table)
 {
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<ModStage> q(new (std::nothrow) ModStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<ModStage>();
+    if (!q) return nullptr;
     q->qam = qam; q->P = P; q->b = b; q->msb = msb;
     q->in_size = 1; q->out_size = qam ? 8 : 4;
     if (upload(q->d_table, table.data(), table.size() * sizeof(float)) || q->reset()) return nullptr;
@@ -77,43 +76,14 @@ static ModStage *modulator_build(bool qam, unsigned P, int b, int msb, const std
 // hexadecimal floating-point text, each read with strtod and rounded to Float32 - both forms give back the Float32 they were printed from
 static lrhip_stage_t *modulator_create(const char *op)
 {
-    const char *c = strchr(op, ':');
-    const std::string name(op, c ? (size_t)(c - op) : strlen(op));
-    const bool qam = name == "qam";
+    OpFields f;
     long P = 0, b = 0, msb = 0;
     std::vector<float> table;
-    bool have_p = false, have_b = false, have_m = false, have_t = false;
-    while (c) {
-        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
-        if (!eq || (next && eq > next) || eq == k) { set_error("%s: malformed parameter in \"%.64s\" (expected key=value)", name.c_str(), op); return nullptr; }
-        const std::string key(k, (size_t)(eq - k));
-        const char *v = eq + 1, *vend = next ? next : v + strlen(v);
-        bool *have = key == "period" ? &have_p : key == "bits" ? &have_b : key == "msb" ? &have_m : key == "table" ? &have_t : nullptr;
-        if (!have) { set_error("%s: unknown parameter \"%s\"", name.c_str(), key.c_str()); return nullptr; }
-        if (*have) { set_error("%s: parameter \"%s\" given twice", name.c_str(), key.c_str()); return nullptr; }
-        *have = true;
-        if (key == "table") {
-            while (v < vend) {
-                char *end = nullptr;
-                const double d = strtod(v, &end);
-                if (end == v || end > vend || (end < vend && *end != ',')) { set_error("%s: bad table entry %zu", name.c_str(), table.size()); return nullptr; }
-                table.push_back((float)d);
-                v = end < vend ? end + 1 : end;
-                if (end < vend && v == vend) { set_error("%s: the table ends with a comma", name.c_str()); return nullptr; }
-            }
-        } else {
-            char *end = nullptr;
-            errno = 0;
-            const long val = strtol(v, &end, 10);
-            if (v == vend || end != vend || errno == ERANGE) { set_error("%s: bad value for \"%s\" (an integer)", name.c_str(), key.c_str()); return nullptr; }
-            (key == "period" ? P : key == "bits" ? b : msb) = val;
-        }
-        c = next;
-    }
-    if (!have_p || !have_b || !have_m || !have_t) {
-        set_error("%s: missing parameter \"%s\"", name.c_str(), !have_p ? "period" : !have_b ? "bits" : !have_m ? "msb" : "table");
-        return nullptr;
-    }
+    if (!f.split(op, nullptr, {{"period", nullptr}, {"bits", nullptr}, {"msb", nullptr}, {"table", nullptr}}, false) ||
+        !f.integer("period", LONG_MIN, LONG_MAX, P) || !f.integer("bits", LONG_MIN, LONG_MAX, b) || !f.integer("msb", LONG_MIN, LONG_MAX, msb) ||
+        !f.floats("table", table, 0, "table entry", "", "the table ends")) return nullptr;
+    const std::string &name = f.name;
+    const bool qam = name == "qam";
     if (P < 1 || P >= (1l << 30)) { set_error("%s: period must be 1 .. 2^30 - 1 samples per symbol (got %ld)", name.c_str(), P); return nullptr; }
     if (b < 1 || b > MOD_MAX_BITS) { set_error("%s: bits per symbol must be 1 .. %d (got %ld)", name.c_str(), MOD_MAX_BITS, b); return nullptr; }
     if (msb != 0 && msb != 1) { set_error("%s: msb must be 0 or 1", name.c_str()); return nullptr; }

@@ -111,3 +111,30 @@ struct PfbChannelizerStage : lrhip_stage {
         return nframes * K;
     }
 };
+
+// The matrix-core channelizer behind lrhip_channelizer_create (ChannelizerStage, stage_resample.h), which has checked the shape: its W operand
+static ChannelizerStage *channelizer_build(const float *taps, unsigned ntaps, unsigned nchannels)
+{
+    auto q = new_stage<ChannelizerStage>();
+    if (!q) return nullptr;
+    int M = (int)ntaps, K = (int)nchannels, K2 = 2 * K;
+    q->M = M; q->K = K;
+    q->in_size = q->out_size = 8;
+    // W[2i][2c] = Re g, W[2i+1][2c] = -Im g, W[2i][2c+1] = Im g, W[2i+1][2c+1] = Re g,
+    // g_c[i] = h[M-1-i] * exp(+j*2*pi*c*(M-1-i)/K)   (kernels_channelizer.h)
+    std::vector<float> W((size_t)2 * M * K2);
+    const double PI2 = 6.283185307179586476925286766559;
+    for (int i = 0; i < M; i++)
+        for (int c = 0; c < K; c++) {
+            int j = M - 1 - i;
+            double a = PI2 * (double)(((long)c * j) % K) / K, h = taps[j];
+            float gr = (float)(h * std::cos(a)), gi = (float)(h * std::sin(a));
+            W[(size_t)(2 * i) * K2 + 2 * c] = gr;
+            W[(size_t)(2 * i + 1) * K2 + 2 * c] = -gi;
+            W[(size_t)(2 * i) * K2 + 2 * c + 1] = gi;
+            W[(size_t)(2 * i + 1) * K2 + 2 * c + 1] = gr;
+        }
+    if (upload(q->W, W.data(), W.size() * sizeof(float))) return nullptr;
+    if (q->reset()) return nullptr;
+    return q.release();
+}

@@ -120,9 +120,8 @@ struct PfbSynthesizerStage : lrhip_stage {
 
 static PfbSynthesizerStage *pfb_synthesizer_build(const std::vector<float> &g, unsigned nchannels, unsigned oversample)
 {
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PfbSynthesizerStage> q(new (std::nothrow) PfbSynthesizerStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<PfbSynthesizerStage>();
+    if (!q) return nullptr;
     const int M = (int)g.size(), K = (int)nchannels;
     q->M = M; q->K = K; q->R = (int)oversample; q->D = K / q->R;
     q->Q = (M + q->D - 1) / q->D;
@@ -144,43 +143,12 @@ static PfbSynthesizerStage *pfb_synthesizer_build(const std::vector<float> &g, u
 // is looked at.
 static lrhip_stage_t *pfb_synthesizer_create(const char *op)
 {
-    const char *name = "pfb_synthesizer";
-    const char *c = strchr(op, ':');
+    OpFields f;
     long K = 0, R = 0;
     std::vector<float> g;
-    bool have_k = false, have_r = false, have_t = false;
-    while (c) {
-        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
-        if (!eq || (next && eq > next) || eq == k) { set_error("%s: malformed parameter in \"%.64s\" (expected key=value)", name, op); return nullptr; }
-        const std::string key(k, (size_t)(eq - k));
-        const char *v = eq + 1, *vend = next ? next : v + strlen(v);
-        bool *have = key == "channels" ? &have_k : key == "oversample" ? &have_r : key == "taps" ? &have_t : nullptr;
-        if (!have) { set_error("%s: unknown parameter \"%s\"", name, key.c_str()); return nullptr; }
-        if (*have) { set_error("%s: parameter \"%s\" given twice", name, key.c_str()); return nullptr; }
-        *have = true;
-        if (key == "taps") {
-            while (v < vend) {
-                if (g.size() > 65536) break;                 // refused below by its count; no need to read on
-                char *end = nullptr;
-                const double d = strtod(v, &end);
-                if (end == v || end > vend || (end < vend && *end != ',')) { set_error("%s: bad tap %zu (a number)", name, g.size()); return nullptr; }
-                g.push_back((float)d);
-                v = end < vend ? end + 1 : end;
-                if (end < vend && v == vend) { set_error("%s: the taps end with a comma", name); return nullptr; }
-            }
-        } else {
-            char *end = nullptr;
-            errno = 0;
-            const long val = strtol(v, &end, 10);
-            if (v == vend || end != vend || errno == ERANGE || val < 0 || val > 1000000) { set_error("%s: bad value for \"%s\" (an integer)", name, key.c_str()); return nullptr; }
-            (key == "channels" ? K : R) = val;
-        }
-        c = next;
-    }
-    if (!have_k || !have_r || !have_t) {
-        set_error("%s: missing parameter \"%s\"", name, !have_k ? "channels" : !have_r ? "oversample" : "taps");
-        return nullptr;
-    }
+    // (a list of more than 65536 taps is refused below by its count: no need to read on)
+    if (!f.split(op, "pfb_synthesizer", {{"channels", nullptr}, {"oversample", nullptr}, {"taps", nullptr}}, false) || !f.integer("channels", 0, 1000000, K) ||
+        !f.integer("oversample", 0, 1000000, R) || !f.floats("taps", g, 65536, "tap", " (a number)", "the taps end")) return nullptr;
     if (const char *why = PfbSynthesizerStage::refusal((unsigned)g.size(), (unsigned)K, (unsigned)R)) { set_error("%s (got %zu taps, %ld channels)", why, g.size(), K); return nullptr; }
     return pfb_synthesizer_build(g, (unsigned)K, (unsigned)R);
 }

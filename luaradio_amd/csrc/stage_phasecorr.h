@@ -78,16 +78,16 @@ struct PhaseCorrStage : lrhip_stage {
 };
 
 // "binaryphasecorrector:num_samples=N[:sample_interval=I]" (binaryphasecorrector.lua:28-33: I defaults to 32)
-static lrhip_stage_t *phasecorr_create(const std::map<std::string, double> &kv, const char *op)
+static lrhip_stage_t *phasecorr_create(const char *op)
 {
-    auto it = kv.find("num_samples");
-    if (it == kv.end()) { set_error("binaryphasecorrector: missing parameter \"num_samples\" in \"%s\"", op); return nullptr; }
-    const double N = it->second, I = kv.count("sample_interval") ? kv.at("sample_interval") : 32.0;
+    OpFields f;
+    double N = 0.0, I = 0.0;
+    if (!f.split(op, "binaryphasecorrector", {{"num_samples", nullptr}, {"sample_interval", "32"}}, true) || !f.number("num_samples", N) ||
+        !f.number("sample_interval", I)) return nullptr;
     if (!(N >= 1.0 && N <= 16777216.0) || N != floor(N)) { set_error("binaryphasecorrector: num_samples must be an integer in [1, 2^24]"); return nullptr; }
     if (!(I >= 1.0 && I <= 2147483648.0) || I != floor(I)) { set_error("binaryphasecorrector: sample_interval must be an integer in [1, 2^31]"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PhaseCorrStage> q(new (std::nothrow) PhaseCorrStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<PhaseCorrStage>();
+    if (!q) return nullptr;
     q->p.N = (unsigned long long)N;
     q->p.I = (unsigned long long)I;
     int c = 0;                                               // ceil(log2(2N))

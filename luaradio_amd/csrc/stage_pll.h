@@ -77,52 +77,38 @@ struct PllStage : lrhip_stage {
     }
 };
 
-static const std::initializer_list<const char *> pll_keys = {"alpha", "beta", "fmin", "fmax", "mult", "segment", "warmup", "speculate"};
-
 static lrhip_stage_t *pll_create(const char *op)
 {
-    // "port=out" / "port=error" is the one value that is no number: taken out of the string before parse_op reads the rest
-    std::string rest(op), name;
-    std::map<std::string, double> kv;
-    const size_t at = rest.find(":port=");
-    if (at != std::string::npos) {
-        const size_t end = rest.find(':', at + 1);
-        const std::string v = rest.substr(at + 6, end == std::string::npos ? std::string::npos : end - at - 6);
-        if (v != "out" && v != "error") { set_error("pll: port must be \"out\" or \"error\", not \"%s\"", v.c_str()); return nullptr; }
-        rest.erase(at, end == std::string::npos ? std::string::npos : end - at);
-        if (rest.find(":port=") != std::string::npos) { set_error("pll: parameter \"port\" given twice"); return nullptr; }
-        kv["port"] = v == "error" ? 1.0 : 0.0;
-    }
-    {
-        std::map<std::string, double> nums;
-        if (!parse_op(rest.c_str(), name, nums, pll_keys)) return nullptr;
-        kv.insert(nums.begin(), nums.end());
-    }
+    OpFields f;
+    if (!f.split(op, "pll", {{"alpha", nullptr}, {"beta", nullptr}, {"fmin", nullptr}, {"fmax", nullptr}, {"mult", "1"}, {"port", "out"},      // pll.lua:32: mult = 1
+                             {"segment", ""}, {"warmup", ""}, {"speculate", "1"}}, true)) return nullptr;
     PllParams p;
-    struct { const char *k; double *v; } need[] = {{"alpha", &p.alpha}, {"beta", &p.beta}, {"fmin", &p.fmin}, {"fmax", &p.fmax}};
-    for (auto &f : need) {
-        auto it = kv.find(f.k);
-        if (it == kv.end()) { set_error("pll: missing parameter \"%s\" in \"%s\"", f.k, op); return nullptr; }
-        if (!std::isfinite(it->second)) { set_error("pll: %s must be finite", f.k); return nullptr; }
-        *f.v = it->second;
+    struct { const char *k; double *v; } nums[] = {{"alpha", &p.alpha}, {"beta", &p.beta}, {"fmin", &p.fmin}, {"fmax", &p.fmax}, {"mult", &p.mult}};
+    for (auto &n : nums) {
+        if (!f.number(n.k, *n.v)) return nullptr;
+        if (!std::isfinite(*n.v)) { set_error("pll: %s must be finite", n.k); return nullptr; }
     }
-    p.mult = kv.count("mult") ? kv.at("mult") : 1.0;         // pll.lua:32
-    if (!std::isfinite(p.mult)) { set_error("pll: mult must be finite"); return nullptr; }
-    const double port = kv.count("port") ? kv.at("port") : 0.0, seg = kv.count("segment") ? kv.at("segment") : 0.0,
-                 warm = kv.count("warmup") ? kv.at("warmup") : -1.0, spec = kv.count("speculate") ? kv.at("speculate") : 1.0;
-    if (spec != 0.0 && spec != 1.0) { set_error("pll: speculate must be 0 or 1"); return nullptr; }
-    if (kv.count("segment") && (!(seg >= 1.0 && seg <= 1073741824.0) || seg != floor(seg))) { set_error("pll: segment must be an integer in [1, 2^30]"); return nullptr; }
-    if (kv.count("warmup") && (!(warm >= 1.0 && warm <= 1073741824.0) || warm != floor(warm))) { set_error("pll: warmup must be an integer in [1, 2^30]"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PllStage> q(new (std::nothrow) PllStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    const int port = f.word("port", {"out", "error"}, "pll: port must be \"out\" or \"error\", not \"", "\"");
+    if (port < 0) return nullptr;
+    bool spec = true;
+    if (!f.flag("speculate", spec)) return nullptr;
+    double seg = 0.0, warm = -1.0;
+    struct { const char *k; double *v; } knobs[] = {{"segment", &seg}, {"warmup", &warm}};
+    for (auto &n : knobs) {
+        if (!f.has(n.k)) continue;
+        if (!f.number(n.k, *n.v)) return nullptr;
+        if (!(*n.v >= 1.0 && *n.v <= 1073741824.0) || *n.v != floor(*n.v)) { set_error("pll: %s must be an integer in [1, 2^30]", n.k); return nullptr; }
+    }
+    auto q = new_stage<PllStage>();
+    if (!q) return nullptr;
     q->p = p;
-    q->port = port == 0.0 ? PLL_PORT_OUT : PLL_PORT_ERROR;
+    q->port = port == 0 ? PLL_PORT_OUT : PLL_PORT_ERROR;
     q->seg_req = (unsigned long)seg;
-    q->W = kv.count("warmup") ? (unsigned long)warm : pll_warmup(p.alpha, p.beta, PLL_TOL_PHI / 256.0);
-    q->allow = spec != 0.0;
+    q->W = f.has("warmup") ? (unsigned long)warm : pll_warmup(p.alpha, p.beta, PLL_TOL_PHI / 256.0);
+    q->allow = spec;
     q->in_size = 8;
     q->out_size = q->port == PLL_PORT_OUT ? 8 : 4;
     if (q->reset()) return nullptr;
     return q.release();
 }
+

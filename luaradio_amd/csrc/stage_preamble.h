@@ -69,31 +69,11 @@ struct PsStage : lrhip_stage {
 // "preamblesampler:period=T:num_samples=N:preamble=0101...": T and N integers, preamble a string of 0 / 1 characters
 static lrhip_stage_t *preamblesampler_create(const char *op)
 {
+    OpFields f;
     long T = 0, N = 0;
     std::string bits;
-    bool have_t = false, have_n = false, have_p = false;
-    const char *c = strchr(op, ':');
-    while (c) {
-        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
-        if (!eq || (next && eq > next) || eq == k) { set_error("preamblesampler: malformed parameter in \"%s\" (expected key=value)", op); return nullptr; }
-        const std::string key(k, (size_t)(eq - k)), val(eq + 1, next ? (size_t)(next - eq - 1) : strlen(eq + 1));
-        bool *have = key == "period" ? &have_t : key == "num_samples" ? &have_n : key == "preamble" ? &have_p : nullptr;
-        if (!have) { set_error("preamblesampler: unknown parameter \"%s\"", key.c_str()); return nullptr; }
-        if (*have) { set_error("preamblesampler: parameter \"%s\" given twice", key.c_str()); return nullptr; }
-        *have = true;
-        if (key == "preamble") {
-            if (val.find_first_not_of("01") != std::string::npos) { set_error("preamblesampler: preamble must be a string of 0 / 1 characters, got \"%s\"", val.c_str()); return nullptr; }
-            bits = val;
-        } else {
-            char *end = nullptr;
-            errno = 0;
-            const long v = strtol(val.c_str(), &end, 10);
-            if (val.empty() || *end || errno == ERANGE || v > 0x7fffffffl || v < -0x7fffffffl) { set_error("preamblesampler: bad value for \"%s\" in \"%s\" (an integer)", key.c_str(), op); return nullptr; }
-            (key == "period" ? T : N) = v;
-        }
-        c = next;
-    }
-    if (!have_t || !have_n || !have_p) { set_error("preamblesampler: missing parameter \"%s\" in \"%s\"", !have_t ? "period" : !have_n ? "num_samples" : "preamble", op); return nullptr; }
+    if (!f.split(op, "preamblesampler", {{"period", nullptr}, {"num_samples", nullptr}, {"preamble", nullptr}}, true) ||
+        !f.integer("period", -0x7fffffffl, 0x7fffffffl, T) || !f.integer("num_samples", -0x7fffffffl, 0x7fffffffl, N) || !f.bits("preamble", bits)) return nullptr;
     // preamblesampler.lua:108-121: with a period of 1 the offset becomes 0 and is decremented before it is tested, with one sample per frame
     // the bit count is past num_samples before it is compared - either way the reference never leaves SAMPLING
     if (T < 2) { set_error("preamblesampler: period must be >= 2 samples per symbol (got %ld)", T); return nullptr; }
@@ -103,9 +83,8 @@ static lrhip_stage_t *preamblesampler_create(const char *op)
     long long B = 1;
     while (B < TL + 1 && B <= PS_MAX_B) B *= 2;                  // 2^ceil_log2(T L + 1), preamblesampler.lua:52
     if (B > PS_MAX_B) { set_error("preamblesampler: period * preamble length = %lld needs a buffer above the limit of %lld samples", TL, PS_MAX_B); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<PsStage> q(new (std::nothrow) PsStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<PsStage>();
+    if (!q) return nullptr;
     q->p = PsParams{(int)T, (int)bits.size(), (int)N, B};
     q->pre_bits.assign((bits.size() + 31) / 32, 0u);
     for (size_t k = 0; k < bits.size(); k++)
@@ -156,15 +135,15 @@ struct MdStage : lrhip_stage {
     }
 };
 
-static lrhip_stage_t *manchesterdecoder_create(const std::map<std::string, double> &kv, const char *op)
+// "manchesterdecoder:invert=0|1"
+static lrhip_stage_t *manchesterdecoder_create(const char *op)
 {
-    auto it = kv.find("invert");
-    if (it == kv.end()) { set_error("manchesterdecoder: missing parameter \"invert\" in \"%s\"", op); return nullptr; }
-    if (it->second != 0.0 && it->second != 1.0) { set_error("manchesterdecoder: invert must be 0 or 1"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<MdStage> q(new (std::nothrow) MdStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    q->invert = it->second != 0.0;
+    OpFields f;
+    bool invert = false;
+    if (!f.split(op, "manchesterdecoder", {{"invert", nullptr}}, true) || !f.flag("invert", invert)) return nullptr;
+    auto q = new_stage<MdStage>();
+    if (!q) return nullptr;
+    q->invert = invert;
     q->in_size = q->out_size = 1;
     if (q->reset()) return nullptr;
     return q.release();

@@ -72,78 +72,38 @@ static uint64_t source_turns(double x)
     return f >= 18446744073709551616.0 ? 0ull : (uint64_t)f;
 }
 
-// "name:key=value:...": every key of `allowed` exactly once, values kept as text
-static bool source_split(const char *op, std::string &name, std::map<std::string, std::string> &kv, std::initializer_list<const char *> allowed)
-{
-    const char *c = strchr(op, ':');
-    name.assign(op, c ? (size_t)(c - op) : strlen(op));
-    while (c) {
-        const char *k = c + 1, *eq = strchr(k, '='), *next = strchr(k, ':');
-        if (!eq || (next && eq > next) || eq == k) { set_error("%s: malformed parameter in \"%.96s\" (expected key=value)", name.c_str(), op); return false; }
-        const std::string key(k, (size_t)(eq - k));
-        bool ok = false;
-        for (const char *a : allowed) ok = ok || key == a;
-        if (!ok) { set_error("%s: unknown parameter \"%s\"", name.c_str(), key.c_str()); return false; }
-        if (kv.count(key)) { set_error("%s: parameter \"%s\" given twice", name.c_str(), key.c_str()); return false; }
-        kv[key] = std::string(eq + 1, next ? (size_t)(next - eq - 1) : strlen(eq + 1));
-        c = next;
-    }
-    for (const char *a : allowed)
-        if (!kv.count(a)) { set_error("%s: missing parameter \"%s\"", name.c_str(), a); return false; }
-    return true;
-}
-static bool source_double(const std::string &name, const std::map<std::string, std::string> &kv, const char *key, double &out)
-{
-    const std::string &v = kv.at(key);
-    char *end = nullptr;
-    errno = 0;
-    out = strtod(v.c_str(), &end);
-    if (v.empty() || *end || errno == ERANGE || !std::isfinite(out)) { set_error("%s: bad value for \"%s\" (a finite number)", name.c_str(), key); return false; }
-    return true;
-}
-
 static lrhip_stage_t *source_create(const char *op)
 {
-    std::string name;
-    std::map<std::string, std::string> kv;
+    OpFields f;
     const bool random = !strncmp(op, "uniformrandomsource", 19);
-    if (random ? !source_split(op, name, kv, {"type", "lo", "hi", "seed"})
-               : !source_split(op, name, kv, {"signal", "frequency", "rate", "amplitude", "phase", "offset"})) return nullptr;
+    if (random ? !f.split(op, nullptr, {{"type", nullptr}, {"lo", nullptr}, {"hi", nullptr}, {"seed", nullptr}}, false)
+               : !f.split(op, nullptr, {{"signal", nullptr}, {"frequency", nullptr}, {"rate", nullptr}, {"amplitude", nullptr}, {"phase", nullptr}, {"offset", nullptr}}, false))
+        return nullptr;
+    const std::string &name = f.name;
     std::unique_ptr<SourceStage> q(new (std::nothrow) SourceStage());
     if (!q) { set_error("out of memory"); return nullptr; }
     q->random = random;
     q->in_size = 0;
     if (!random) {
-        static const char *const names[] = {"exponential", "cosine", "sine", "square", "triangle", "sawtooth", "constant"};
-        int sig = -1;
-        for (int i = 0; i < 7; i++)
-            if (kv["signal"] == names[i]) sig = i;
-        if (sig < 0) { set_error("Unsupported signal (\"%s\")", kv["signal"].c_str()); return nullptr; }       // signal.lua:50
+        const int sig = f.word("signal", {"exponential", "cosine", "sine", "square", "triangle", "sawtooth", "constant"},       // the order of SRC_*
+                               "Unsupported signal (\"", "\")");                                                                 // signal.lua:50
+        if (sig < 0) return nullptr;
         double frequency, rate, phase;
-        if (!source_double(name, kv, "frequency", frequency) || !source_double(name, kv, "rate", rate) || !source_double(name, kv, "amplitude", q->amp) ||
-            !source_double(name, kv, "phase", phase) || !source_double(name, kv, "offset", q->off)) return nullptr;
+        if (!f.number("frequency", frequency, true) || !f.number("rate", rate, true) || !f.number("amplitude", q->amp, true) ||
+            !f.number("phase", phase, true) || !f.number("offset", q->off, true)) return nullptr;
         if (!(rate > 0.0)) { set_error("%s: rate must be positive", name.c_str()); return nullptr; }
         q->sig = sig;
         q->step = source_turns(frequency / rate);
         q->p0 = source_turns(phase / 6.283185307179586);
         q->out_size = sig == SRC_EXPONENTIAL ? 8 : 4;
     } else {
-        static const char *const names[] = {"cf32", "f32", "byte", "bit"};
-        int t = -1;
-        for (int i = 0; i < 4; i++)
-            if (kv["type"] == names[i]) t = i;
-        if (t < 0) { set_error("%s: unsupported type \"%s\" (cf32, f32, byte or bit)", name.c_str(), kv["type"].c_str()); return nullptr; }
+        const int t = f.word("type", {"cf32", "f32", "byte", "bit"}, "uniformrandomsource: unsupported type \"", "\" (cf32, f32, byte or bit)");      // the order of RND_*
+        if (t < 0) return nullptr;
         double lo, hi;
-        if (!source_double(name, kv, "lo", lo) || !source_double(name, kv, "hi", hi)) return nullptr;
+        if (!f.number("lo", lo, true) || !f.number("hi", hi, true)) return nullptr;
         if (lo > hi) { set_error("%s: lo must not exceed hi", name.c_str()); return nullptr; }
-        const std::string &sv = kv["seed"];
-        char *end = nullptr;
-        errno = 0;
-        const unsigned long long seed = strtoull(sv.c_str(), &end, 10);
-        if (sv.empty() || sv.find_first_not_of("0123456789") != std::string::npos || *end || errno == ERANGE) {
-            set_error("%s: bad value for \"seed\" (a decimal integer below 2^64)", name.c_str());
-            return nullptr;
-        }
+        uint64_t seed = 0;
+        if (!f.u64("seed", seed)) return nullptr;
         q->rtype = t;
         q->rnd.seed = seed;
         q->rnd.lo = lo;

@@ -70,9 +70,8 @@ struct FftStage : lrhip_stage {
 static FftStage *fft_build(unsigned n)
 {
     if (n < 8 || n > 4096 || (n & (n - 1))) { set_error("fft: frame length must be a power of two in [8, 4096] (got %u)", n); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<FftStage> q(new (std::nothrow) FftStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
+    auto q = new_stage<FftStage>();
+    if (!q) return nullptr;
     q->N = (int)n;
     q->fpw = n >= 512 ? 1 : (int)(512 / n);
     std::vector<float> tw(n);   // n/2 complex
