@@ -2,6 +2,19 @@
 // (part of liblrhip.so; included by lrhip.hip in this order, one translation unit)
 #pragma once
 #include "fir_form.h"
+#include "launch_prep.h"
+
+// the kernel instantiation for a raw record format (RX_FMT_U8 / S8 / S16LE; kernels_fir.h): fn(std::integral_constant<int, RX_FMT_*>{}).  ComplexFloat32
+// samples are no record format: the callers that take them too name that instantiation themselves
+template <typename Fn>
+static int with_record_format(int fmt, Fn fn)
+{
+    switch (fmt) {
+        case RX_FMT_U8: return fn(std::integral_constant<int, RX_FMT_U8>{});
+        case RX_FMT_S8: return fn(std::integral_constant<int, RX_FMT_S8>{});
+        default: return fn(std::integral_constant<int, RX_FMT_S16LE>{});
+    }
+}
 
 // =====================================================================================================
 // FIRFilterBlock (+ fused FrequencyTranslatorBlock in front, + fused DownsamplerBlock behind)
@@ -22,7 +35,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         return h;
     }
     DeviceBuf d_taps, d_atab, d_ctaps4;
-    int mfma_blocks_per_cu = 0;           // resident workgroups of the persistent kernel (occupancy query, cached)
     int hist_pad = 0;                     // leading pad floats in the history buffers (1 for complex taps, see launch_mfma_cc)
     DeviceBuf hist[2];
     int cur = 0;
@@ -40,10 +52,9 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     DeviceBuf d_fft_tables;
     DeviceBuf d_fft4k_tables;             // 513 .. 1281 taps on a ComplexFloat32 stream: the 4096-point kernel (kernels_firfft4k.h)
     DeviceBuf d_fft64_tables;             // ... and its one-wave-per-block form (kernels_firfft64.h)
-    int fft4k_blocks = 0, fft_blocks_per_cu = 0;
+    int fft_blocks_per_cu = 0;
     int mode_req = 0;                     // use_fft as the caller passed it (0..3), before 3 = automatic was resolved
     DeviceBuf d_dec_tables;
-    int dec_blocks_per_cu = 0;
     double rot_omega = 0.0;
     bool hist_in_kernel = false;          // set by a launch that also wrote the next history buffer
     int post_unary = 0;      // 1 + UN_CMAG / UN_CPHASE / UN_CREAL / UN_CIMAG folded into the LDS-staged decimator's store (chains: tuner -> ComplexMagnitude ...), Float32 out
@@ -113,6 +124,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         else return set_error("internal: no persistent Toeplitz kernel at decimation %d", DD);
     }
 
+    // The overlap-save launches (launch_fft, launch_fft64, launch_fft64_long) keep their own preparation, per stage
     template <typename K>
     int prepare_kernel(K kern, size_t lds_bytes, int *blocks_per_cu, int threads = 256)
     {
@@ -124,9 +136,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         }
         return 0;
     }
-
-    // a stage launches several instantiations over its life (raw records / converted samples on edge chunks, the bit-exact and the window-relative
-    // rotator): each gets its own attribute call and its own occupancy figure, queried once.  Returns workgroups per CU, or -1.
     std::vector<std::pair<const void *, int>> prepared;
     template <typename K>
     int prepared_blocks(K kern, size_t lds_bytes, int threads = 256)
@@ -166,10 +175,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         uint64_t rs = rot ? rot_step : 0, rc = rot ? count : 0;
         if constexpr (KS > 0) {
             auto launch = [&](auto kern) -> int {
-                if ((mfma_blocks_per_cu = prepared_blocks(kern, lds_bytes, 64 * NW)) < 0) return -1;     // queried once per instantiation
-                long slots = (long)ctx().num_cus * mfma_blocks_per_cu;
-                const int rounds = ntiles > slots && fir_knobs().fir_rounds > 0 ? fir_knobs().fir_rounds : 0;      // tile order (LRHIP_FIR_ROUNDS)
-                unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
+                const long slots = chip_slots(kern, 64 * NW, lds_bytes);
+                if (slots < 0) return -1;
+                const int rounds = persistent_rounds(ntiles, slots, fir_knobs().fir_rounds);      // tile order (LRHIP_FIR_ROUNDS)
+                const unsigned grid = persistent_grid(ntiles, slots, rounds);
                 if (post_disc && edge.reserve((size_t)ntiles * 2 * NW * sizeof(float2))) return -1;
                 float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds_bytes, ctx().stream, h, x, atab, y, M, n, n_out, (long)index, e,
@@ -215,14 +224,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             if (post_disc) return set_error("internal: discriminator epilogue without a persistent kernel variant");
             if constexpr (SS == 2 && DD == 5 && KS == 51 && NW == 4) {
                 if (raw_now) {
-                    if (rot)
-                        rc2 = in_fmt == RX_FMT_U8 ? launch(fir_mfma_persistent_kernel<2, DD, NACC, true, KS, 0, false, 4, RX_FMT_U8>)
-                            : in_fmt == RX_FMT_S8 ? launch(fir_mfma_persistent_kernel<2, DD, NACC, true, KS, 0, false, 4, RX_FMT_S8>)
-                                                  : launch(fir_mfma_persistent_kernel<2, DD, NACC, true, KS, 0, false, 4, RX_FMT_S16LE>);
-                    else
-                        rc2 = in_fmt == RX_FMT_U8 ? launch(fir_mfma_persistent_kernel<2, DD, NACC, false, KS, 0, false, 4, RX_FMT_U8>)
-                            : in_fmt == RX_FMT_S8 ? launch(fir_mfma_persistent_kernel<2, DD, NACC, false, KS, 0, false, 4, RX_FMT_S8>)
-                                                  : launch(fir_mfma_persistent_kernel<2, DD, NACC, false, KS, 0, false, 4, RX_FMT_S16LE>);
+                    auto raw = [&](auto r) {
+                        return with_record_format(in_fmt, [&](auto fmt) { return launch(fir_mfma_persistent_kernel<2, DD, NACC, decltype(r)::value, KS, 0, false, 4, decltype(fmt)::value>); });
+                    };
+                    rc2 = rot ? raw(std::true_type{}) : raw(std::false_type{});
                     if (rc2) return rc2;
                     LR_LAUNCH_CHECK();
                     return 0;
@@ -238,7 +243,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         } else {
             if (post_disc) return set_error("internal: discriminator epilogue without a persistent kernel variant");
             auto launch = [&](auto kern) -> int {
-                if (prepare_kernel(kern, lds_bytes, nullptr)) return -1;
+                if (kernel_allow_lds(kern, lds_bytes)) return -1;
                 hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds_bytes, ctx().stream, h, x, atab, y, M, n, n_out, (long)index, e,
                                    ksteps, out_aligned, rs, rc);
                 return 0;
@@ -255,20 +260,15 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     // HilbertTransformBlock in one launch (hilbert_ok): the generic Float32 Toeplitz kernel with the pair epilogue (kernels_fir.h, HILB).  y2 receives n
     // ComplexFloat32 samples (delayed input, filtered input); history / index bookkeeping is core()'s (D = 1: index stays 0)
     // the window form (kernels_firwin.h hilbert_win_kernel): the reference's tap counts, taps at even distance from the centre exactly zero
-    int hilb_sparse = -1, hilb_blocks = 0;
+    int hilb_sparse = -1;
     template <int MM>
     int launch_hilbert_win(const float *x, long n, float *y2)
     {
         using G = FwhGeom<MM>;
         const size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
         auto kern = hilbert_win_kernel<MM>;
-        if (!hilb_blocks) {
-            if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            int nb_ = 0;
-            LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, kern, 256, lds_bytes));
-            hilb_blocks = nb_ < 1 ? 1 : nb_;
-        }
-        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE, slots = (long)ctx().num_cus * hilb_blocks;
+        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE, slots = chip_slots(kern, 256, lds_bytes);
+        if (slots < 0) return -1;
         long run = (ntiles + 4 * slots - 1) / (4 * slots);
         if (fir_knobs().hilbert_run > 0) run = fir_knobs().hilbert_run;      // A/B knob: tiles per workgroup
         const unsigned grid = (unsigned)((ntiles + run - 1) / run);
@@ -297,7 +297,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const size_t lds_bytes = ((size_t)fir_taps_len(1, ksteps) + (size_t)G::phys(span) + G::PAD + 8) * sizeof(float);
         const long ntiles = (n + TILE_OUT - 1) / TILE_OUT;
         auto kern = fir_mfma_kernel<1, 1, NACC, false, 1, true>;
-        if (prepare_kernel(kern, lds_bytes, nullptr)) return -1;
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float *)d_atab.p, y2, M, n, n,
                            (long)index, e, ksteps, (int)(((uintptr_t)y2 % 16) == 0), (uint64_t)0, (uint64_t)0);
         LR_LAUNCH_CHECK();
@@ -332,7 +332,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const float *h = (const float *)hist[cur].p;          // includes the pad float
         int out_aligned = ((uintptr_t)y % 16) == 0;
         auto kern = fir_mfma_kernel<1, DD2, NACC, false, 2>;
-        if (prepare_kernel(kern, lds_bytes, nullptr)) return -1;
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds_bytes, ctx().stream, h, x, atab, y, M2, n2, n_out, first2, e,
                            ksteps, out_aligned, (uint64_t)0, (uint64_t)0);
         LR_LAUNCH_CHECK();
@@ -352,21 +352,20 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     }
 
     template <int VV, int NG>
-    int launch_fft4k_ng(const float *x, long n, float *y, long n_out, int *blocks_per_cu)
+    int launch_fft4k_ng(const float *x, long n, float *y, long n_out)
     {
         constexpr long Lf = F4K_N - VV;
         const size_t lds_bytes = (size_t)f4k_lds_elems(NG) * sizeof(float2);
         auto kern = fir_fft4k_kernel<VV, NG>;
-        if (!*blocks_per_cu && prepare_kernel(kern, lds_bytes, blocks_per_cu, 256 * NG)) return -1;
-        const long nblocks = (n_out + Lf - 1) / Lf, nslots = (nblocks + NG - 1) / NG, slots = (long)ctx().num_cus * *blocks_per_cu;
-        const unsigned grid = (unsigned)(nslots < slots ? nslots : slots);
+        const long nblocks = (n_out + Lf - 1) / Lf, nslots = (nblocks + NG - 1) / NG, slots = chip_slots(kern, 256 * NG, lds_bytes);
+        if (slots < 0) return -1;
+        const unsigned grid = persistent_grid(nslots, slots, 0);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * NG), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft4k_tables.p, y, M, n,
                            n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, fir_knobs().f4k_xcd_map);      // (XCD-major block order)
         LR_LAUNCH_CHECK();
         hist_in_kernel = true;
         return 0;
     }
-    int fft4k_blocks2 = 0;
     // one WAVE per 4096-point block as 64 x 64 (kernels_firfft64.h): eight waves per CU with the conjugate-symmetric H of real taps, four with complex taps
     template <int VV, int WAVES, int SS = 2, bool HG = false>
     int launch_fft64(const float *x, long n, float *y, long n_out)
@@ -416,7 +415,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     template <int VV>
     int launch_fft4k(const float *x, long n, float *y, long n_out)
     {
-        return fir_knobs().f4k_ng == 2 ? launch_fft4k_ng<VV, 2>(x, n, y, n_out, &fft4k_blocks2) : launch_fft4k_ng<VV, 1>(x, n, y, n_out, &fft4k_blocks);
+        return fir_knobs().f4k_ng == 2 ? launch_fft4k_ng<VV, 2>(x, n, y, n_out) : launch_fft4k_ng<VV, 1>(x, n, y, n_out);
     }
     // ---- partitioned overlap-save (kernels_firpols.h, round 4): 513 taps and more in one launch per 1 536 taps, ComplexFloat32 or Float32 stream
     template <int SS, int PP>
@@ -425,7 +424,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const size_t lds_bytes = (size_t)pols_lds_elems(SS, PP) * sizeof(float2);
         constexpr int POLS_WPB = pols_wpb(SS, PP);
         auto kern = fir_pols_kernel<SS, PP>;
-        if (prepared_blocks(kern, lds_bytes, 64 * POLS_WPB) < 0) return -1;
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         // a wave owns a run of consecutive blocks (its spectra delay line); runs of ~40 blocks keep the P - 1 warm-up blocks of a run under 5 %,
         // and the number of runs is a whole number of rounds of (CUs x waves) where the launch is long enough
         constexpr long RPW = SS == 2 ? 1 : 2;
@@ -568,7 +567,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     }
 
     // decimations without a Toeplitz instantiation (and taps too long for its LDS table): LDS-staged one-output-per-thread kernel, first or second form (decim_lds2_ok)
-    int decim_blocks_per_cu = 0;
     int launch_decim_lds(bool v2, const float *x, long n, float *y, long n_out)
     {
         // staged samples per tile: the kernel's registers allow DECIM_SPAN_MAX; LRHIP_DECIM_SPAN (A/B) asks for less = smaller tiles, more workgroups per CU
@@ -585,27 +583,20 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                               : ((size_t)(((taps_complex ? 2 : 1) * M + 3) & ~3) + (size_t)S * (span + (span >> 5) + 2)) * sizeof(float);
         const float *h = (const float *)hist[cur].p + hist_pad;
         float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
-        auto go = [&](auto kern) -> int {
-            if ((decim_blocks_per_cu = prepared_blocks(kern, lds_bytes)) < 0) return -1;
-            long slots = (long)ctx().num_cus * decim_blocks_per_cu;
-            const int rounds = ntiles > slots && fir_knobs().decim_rounds > 0 ? fir_knobs().decim_rounds : 0;
-            unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index, (long)D, OW,
-                               ntiles, rot ? rot_step : (uint64_t)0, rot ? count : (uint64_t)0, ho, post_unary, rounds);
+        // (more: what the second form's kernels take behind `rounds`)
+        auto go = [&](auto kern, auto... more) -> int {
+            const long slots = chip_slots(kern, 256, lds_bytes);
+            if (slots < 0) return -1;
+            const int rounds = persistent_rounds(ntiles, slots, fir_knobs().decim_rounds);
+            hipLaunchKernelGGL(kern, dim3(persistent_grid(ntiles, slots, rounds)), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index,
+                               (long)D, OW, ntiles, rot ? rot_step : (uint64_t)0, rot ? count : (uint64_t)0, ho, post_unary, rounds, more...);
             hist_in_kernel = ho != nullptr;
             return 0;
         };
         auto go2 = [&](auto kern) -> int {
-            if ((decim_blocks_per_cu = prepared_blocks(kern, lds_bytes)) < 0) return -1;
-            long slots = (long)ctx().num_cus * decim_blocks_per_cu;
-            const int rounds = ntiles > slots && fir_knobs().decim_rounds > 0 ? fir_knobs().decim_rounds : 0;
-            unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots);
             float2 *dp = (float2 *)disc_prev.p;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index, (long)D, OW,
-                               ntiles, rot ? rot_step : (uint64_t)0, rot ? count : (uint64_t)0, ho, post_unary, rounds, 1.0 / disc_gain,
-                               dsc ? (const float2 *)(dp + disc_cur) : (const float2 *)nullptr, dsc ? dp + (disc_cur ^ 1) : (float2 *)nullptr,
-                               rel_rot ? 0 : 1);      // an exact chain keeps one fmaf chain per output (no tap split over the half-waves)
-            hist_in_kernel = ho != nullptr;
+            if (go(kern, 1.0 / disc_gain, dsc ? (const float2 *)(dp + disc_cur) : (const float2 *)nullptr, dsc ? dp + (disc_cur ^ 1) : (float2 *)nullptr,
+                   rel_rot ? 0 : 1)) return -1;      // an exact chain keeps one fmaf chain per output (no tap split over the half-waves)
             if (dsc) disc_cur ^= 1;
             return 0;
         };
@@ -613,20 +604,17 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         if (v2) {
             auto pick = [&](auto ph) -> int {
                 constexpr bool PH = decltype(ph)::value;
-                if (raw_now)
-                    return rot ? (in_fmt == RX_FMT_U8 ? go2(fir_decim_lds2_kernel<true, RX_FMT_U8, PH>) : in_fmt == RX_FMT_S8 ? go2(fir_decim_lds2_kernel<true, RX_FMT_S8, PH>)
-                                                                                                        : go2(fir_decim_lds2_kernel<true, RX_FMT_S16LE, PH>))
-                               : (in_fmt == RX_FMT_U8 ? go2(fir_decim_lds2_kernel<false, RX_FMT_U8, PH>) : in_fmt == RX_FMT_S8 ? go2(fir_decim_lds2_kernel<false, RX_FMT_S8, PH>)
-                                                                                                         : go2(fir_decim_lds2_kernel<false, RX_FMT_S16LE, PH>));
+                if (raw_now) {
+                    auto raw = [&](auto r) { return with_record_format(in_fmt, [&](auto fmt) { return go2(fir_decim_lds2_kernel<decltype(r)::value, decltype(fmt)::value, PH>); }); };
+                    return rot ? raw(std::true_type{}) : raw(std::false_type{});
+                }
                 return rot ? go2(fir_decim_lds2_kernel<true, RX_FMT_CF32, PH>) : go2(fir_decim_lds2_kernel<false, RX_FMT_CF32, PH>);
             };
             rc = decim2_esh((long)D) ? pick(std::true_type{}) : pick(std::false_type{});
         } else if (raw_now) {
             if (taps_complex || S != 2) return set_error("internal: raw records reached a kernel without a record instantiation");
-            rc = rot ? (in_fmt == RX_FMT_U8 ? go(fir_decim_lds_kernel<2, true, false, RX_FMT_U8>) : in_fmt == RX_FMT_S8 ? go(fir_decim_lds_kernel<2, true, false, RX_FMT_S8>)
-                                                                                               : go(fir_decim_lds_kernel<2, true, false, RX_FMT_S16LE>))
-                     : (in_fmt == RX_FMT_U8 ? go(fir_decim_lds_kernel<2, false, false, RX_FMT_U8>) : in_fmt == RX_FMT_S8 ? go(fir_decim_lds_kernel<2, false, false, RX_FMT_S8>)
-                                                                                               : go(fir_decim_lds_kernel<2, false, false, RX_FMT_S16LE>));
+            auto raw = [&](auto r) { return with_record_format(in_fmt, [&](auto fmt) { return go(fir_decim_lds_kernel<2, decltype(r)::value, false, decltype(fmt)::value>); }); };
+            rc = rot ? raw(std::true_type{}) : raw(std::false_type{});
         } else
         rc = taps_complex ? go(fir_decim_lds_kernel<2, false, true>)
                  : S == 2 ? (rot ? go(fir_decim_lds_kernel<2, true>) : go(fir_decim_lds_kernel<2, false>))
@@ -652,8 +640,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const float *h = (const float *)hist[cur].p + hist_pad;
         float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
         auto go = [&](auto kern) -> int {
-            if (!dec_blocks_per_cu && prepare_kernel(kern, lds_bytes, &dec_blocks_per_cu)) return -1;
-            const long nquads = (pr.nblocks + 3) / 4, slots = (long)ctx().num_cus * dec_blocks_per_cu;
+            const long nquads = (pr.nblocks + 3) / 4, slots = chip_slots(kern, 256, lds_bytes);
+            if (slots < 0) return -1;
             // one-shot order (common.h grid_for): workgroups of 4 waves x `rounds` consecutive quads, handed out in address order.  More
             // quads per wave amortise the table load and the first (unhidden) window request; same-box A/B at 2^26 samples:
             // rounds 1 / 2 / 4 = 0.171 / 0.167 / 0.164 ms
@@ -688,16 +676,14 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         return 0;
     }
 
-    int win_blocks_per_cu = 0;
     template <int MM, bool ONESHOT = false>
     int launch_win_real_m(const float *x, long n, float *y)
     {
         using G = FwrGeom<MM>;
         const size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
         auto kern = fir_win_real_kernel<MM, false>;
-        if (!win_blocks_per_cu && prepare_kernel(kern, lds_bytes, &win_blocks_per_cu)) return -1;
-        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE;
-        const long slots = (long)ctx().num_cus * win_blocks_per_cu;
+        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE, slots = chip_slots(kern, 256, lds_bytes);
+        if (slots < 0) return -1;
         FwrParams pr;
         memset(&pr, 0, sizeof(pr));
         pr.hist = (const float *)hist[cur].p + hist_pad; pr.x = x; pr.n = n; pr.taps_rev = (const float *)d_taps.p; pr.y = y;
@@ -709,7 +695,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         hist_in_kernel = pr.hist_out != nullptr;
         return 0;
     }
-    int winc_blocks_per_cu = 0;           // register-window kernel of kernels_firwin2.h (fir_win_cplx_ok, fir_win_pair_ok, fir_win_short_ok)
+    // register-window kernel of kernels_firwin2.h (fir_win_cplx_ok, fir_win_pair_ok, fir_win_short_ok) and the recurrence fused behind its pair mode
     float iir_b0 = 1.f, iir_na1 = 0.f, iir_na1_lo = 0.f;
     int iir_warm = 1;
     DeviceBuf d_iir_ptab, iir_state[2];
@@ -739,7 +725,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         using G = FwcGeom<DD, 5, MM, MODE>;
         const size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
         auto kern = fir_win_cplx_kernel<DD, 5, MM, MODE>;
-        if (!winc_blocks_per_cu && prepare_kernel(kern, lds_bytes, &winc_blocks_per_cu)) return -1;
+        const long slots = chip_slots(kern, 256, lds_bytes);
+        if (slots < 0) return -1;
         FwcParams pr;
         memset(&pr, 0, sizeof(pr));
         pr.hist = (const float *)hist[cur].p + hist_pad; pr.x = x; pr.n = n; pr.taps_rev = (const float *)(G::CTAPS ? d_ctaps4.p : d_taps.p); pr.y = y;
@@ -752,7 +739,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             pr.prev_in = dp + disc_cur; pr.prev_out = dp + (disc_cur ^ 1);
             pr.inv_gain = 1.0 / disc_gain;
         }
-        const long slots = (long)ctx().num_cus * winc_blocks_per_cu;
         unsigned grid;
         if (G::IIR) {
             pr.b0 = iir_b0; pr.na1 = iir_na1; pr.na1_lo = iir_na1_lo; pr.ptab = (const float *)d_iir_ptab.p; pr.warm_waves = iir_warm;

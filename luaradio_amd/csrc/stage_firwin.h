@@ -16,7 +16,6 @@ struct FirWinRealStage : lrhip_stage {
     float b0 = 0.f, b1 = 0.f, na1 = 0.f;
     int nb = 1, warm_waves = 4;
     unsigned long D = 1, index = 0;
-    int blocks_per_cu = 0;
     const char *kind() const override { return iir ? "fir+iir" : "firwin"; }
     unsigned long max_output(unsigned long n) const override { return D == 1 ? n : n / D + 1; }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
@@ -52,14 +51,8 @@ struct FirWinRealStage : lrhip_stage {
         using G = FwrGeom<MM>;
         const size_t lds_bytes = (size_t)G::LDS_FLOATS * sizeof(float);
         auto kern = fir_win_real_kernel<MM, II>;
-        if (!blocks_per_cu) {
-            if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            int nb_ = 0;
-            LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, kern, 256, lds_bytes));
-            blocks_per_cu = nb_ < 1 ? 1 : nb_;
-        }
-        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE;
-        const long slots = (long)ctx().num_cus * blocks_per_cu;
+        const long ntiles = (n + FWR_TILE - 1) / FWR_TILE, slots = chip_slots(kern, 256, lds_bytes);
+        if (slots < 0) return -1;
         long run = (ntiles + slots - 1) / slots;
         if (II && run < 2 && ntiles > slots / 2) run = 2;          // bound the warm-up share
         FwrParams pr;

@@ -44,7 +44,7 @@ struct PfbChannelizerStage : lrhip_stage {
         const int T = frames_per_tile(), G = frames_per_group();
         size_t lds_bytes = ((size_t)(T + G) * K + K / 2) * sizeof(float2);
         auto kern = pfb_channelizer_kernel<F, NT>;
-        if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + T - 1) / T);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)taps.p,
                            (const float2 *)tw.p, y, M, log2k, P, T, G, n, nframes, (long)index);
@@ -57,7 +57,7 @@ struct PfbChannelizerStage : lrhip_stage {
         if (F > 1 && T % (RR * F)) return set_error("pfb_channelizer: a tile of %d frames does not hold blocks of %d frames in %d classes", T, F, RR);
         size_t lds_bytes = ((size_t)(T + G) * K + K / 2) * sizeof(float2);
         auto kern = pfb_oversampled_kernel<RR, F, NT>;
-        if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + T - 1) / T);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)taps.p,
                            (const float2 *)tw.p, y, M, log2k, P, T, G, n, nframes, (long)index, (int)phase);

@@ -57,7 +57,7 @@ struct PfbSynthesizerStage : lrhip_stage {
         const int T = ifft_tile(), G = ifft_group();
         size_t lds_bytes = ((size_t)(T + G) * K + K / 2) * sizeof(float2);
         auto kern = pfb_synth_ifft_kernel<NT>;
-        if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + T - 1) / T);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, (const float2 *)pend.p, x, (const float2 *)tw.p,
                            (float2 *)scratch.p + (size_t)(Q - 1) * K, log2k, T, G, (long)npend, nframes);

@@ -13,10 +13,8 @@ struct ResampleStage : lrhip_stage {
     int cur = 0;
     uint64_t Q0 = 0, m0 = 0;          // absolute input samples consumed / outputs emitted so far
     int interp_J = 0;                 // > 0: the register-window interpolator kernel applies (kernels_interp.h), taps per phase
-    int rat_blocks_per_cu = 0;
     // (L, D) pairs with a kept-phases instantiation (fir_rational_kernel): 128 taps, ComplexFloat32, gcd(L, D) = 1
     static bool rational_supported(int L, unsigned long D) { return (L == 3 && D == 2) || (L == 2 && D == 3) || (L == 4 && D == 3) || (L == 3 && D == 4) || (L == 5 && D == 4) || (L == 4 && D == 5); }
-    int interp_blocks_per_cu = 0;     // its resident workgroups per CU (occupancy query, cached)
     // Tiles per workgroup of the register-window kernels (kernels_interp.h `rounds`): runs of consecutive tiles, workgroups handed out in address order.
     // 0 = persistent workgroups with a grid stride and a register prefetch of the next tile (rounds 2-3; launches that do not fill the slots keep it).
     // Measured on 2^26 input samples, same box, two alternations (profiles/r04_resampler_tile_order.txt): ONE tile per workgroup is the fastest order for
@@ -27,7 +25,7 @@ struct ResampleStage : lrhip_stage {
     {
         static const char *e = getenv("LRHIP_RESAMPLE_ROUNDS");
         if (e) return atoi(e) < 0 ? 0 : atoi(e);
-        return ntiles <= slots ? 0 : 1;
+        return persistent_rounds(ntiles, slots, 1);
     }
     static constexpr int SPAN_MAX = 6144;
     const char *kind() const override { return "resample"; }
@@ -62,16 +60,10 @@ struct ResampleStage : lrhip_stage {
         if (interp_J > 0 && D == 1 && ((uintptr_t)in_dev & 7) == 0 && ((uintptr_t)out_dev & 7) == 0) {
             // ComplexFloat32 Interpolator(L), 128 taps: a lane owns 5 input positions and all L phases (fir_interp_kernel)
             auto gi = [&](auto kern, size_t lds_bytes, int tq) -> int {
-                if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                if (!interp_blocks_per_cu) {
-                    int nb = 0;
-                    LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, FIP_NT, lds_bytes));
-                    interp_blocks_per_cu = nb < 1 ? 1 : nb;
-                }
-                const long ntiles = ((long)n + tq - 1) / tq, slots = (long)ctx().num_cus * interp_blocks_per_cu;
+                const long ntiles = ((long)n + tq - 1) / tq, slots = chip_slots(kern, FIP_NT, lds_bytes);
+                if (slots < 0) return -1;
                 const int rounds = resample_rounds(ntiles, slots);
-                const long wgs = rounds > 0 ? (ntiles + rounds - 1) / rounds : (ntiles < slots ? ntiles : slots);
-                hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(FIP_NT), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_ttab.p,
+                hipLaunchKernelGGL(kern, dim3(persistent_grid(ntiles, slots, rounds)), dim3(FIP_NT), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_ttab.p,
                                    (float *)out_dev, (long)n, HQ, c, ho, ablation_bits("LRHIP_INTERP_DBG"), rounds);
                 return 0;
             };
@@ -89,16 +81,10 @@ struct ResampleStage : lrhip_stage {
         if (!no_rational && interp_J > 0 && D > 1 && ((uintptr_t)in_dev & 7) == 0 && ((uintptr_t)out_dev & 7) == 0) {
             // ComplexFloat32 RationalResampler(L, D), 128 taps: only the kept (position, phase) pairs, register window (fir_rational_kernel)
             auto gr = [&](auto kern, size_t lds_bytes, int tq) -> int {
-                if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                if (!rat_blocks_per_cu) {
-                    int nb = 0;
-                    LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds_bytes));
-                    rat_blocks_per_cu = nb < 1 ? 1 : nb;
-                }
-                const long ntiles = ((long)n + (long)(Q0 % D) + tq - 1) / tq, slots = (long)ctx().num_cus * rat_blocks_per_cu;
+                const long ntiles = ((long)n + (long)(Q0 % D) + tq - 1) / tq, slots = chip_slots(kern, 256, lds_bytes);
+                if (slots < 0) return -1;
                 const int rounds = resample_rounds(ntiles, slots);
-                const long wgs = rounds > 0 ? (ntiles + rounds - 1) / rounds : (ntiles < slots ? ntiles : slots);
-                hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_ttab.p,
+                hipLaunchKernelGGL(kern, dim3(persistent_grid(ntiles, slots, rounds)), dim3(256), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_ttab.p,
                                    (float *)out_dev, (long)n, n_out, m0, Q0, HQ, c, ho, rounds);
                 return 0;
             };
@@ -121,7 +107,7 @@ struct ResampleStage : lrhip_stage {
         int span_cap = (int)(256 * D / (unsigned long)L) + (M - 1) / L + 4;
         size_t lds_bytes = ((size_t)((((M - 1) / L + 1) * L + 3) & ~3) + (size_t)span_cap * S) * sizeof(float);
         auto go = [&](auto kern) -> int {
-            if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+            if (kernel_allow_lds(kern, lds_bytes)) return -1;
             unsigned grid = n_out > 0 ? (unsigned)((n_out + 255) / 256) : 1;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_taps.p, (float *)out_dev, M, L,
                                (long)D, (long)n, n_out, m0, Q0, HQ, c, span_cap, ho);
@@ -163,7 +149,7 @@ struct ChannelizerStage : lrhip_stage {
         size_t dsize = (size_t)((nflt + 2 * (nflt / K2) + 2 + 3) / 4) * 4;
         size_t lds_bytes = (dsize + (size_t)2 * CHAN_KSLAB * (K2 + 16)) * sizeof(float);
         auto kern = channelizer_kernel<NCT>;
-        if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + CHAN_MT - 1) / CHAN_MT);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)W.p, y, M, n,
                            nframes, (long)index);

@@ -12,7 +12,6 @@ struct FftStage : lrhip_stage {
     float out_scale = 1.f;
     bool has_window = false;
     DeviceBuf tw, window, spec_tables;    // spec_tables: tw1 | tw2 of the one-wave-per-frame N = 1024 engine
-    int spec_blocks_per_cu = 0;
     const char *kind() const override { return "fft"; }
     int reset() override { return 0; }
     unsigned long max_output(unsigned long n) const override { return n - n % N; }
@@ -28,18 +27,11 @@ struct FftStage : lrhip_stage {
                                : (out_kind == FFT_OUT_PSD ? SPEC_FWD_PSD : out_kind == FFT_OUT_PSD_LOG ? SPEC_FWD_PSD_LOG : SPEC_FWD_COMPLEX);
             const float *wp = has_window ? (const float *)window.p : nullptr;
             auto go = [&](auto kern) -> int {
-                if (!spec_blocks_per_cu) {
-                    if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                    int nb = 0;
-                    LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds_bytes));
-                    spec_blocks_per_cu = nb < 1 ? 1 : nb;
-                }
-                long slots = (long)ctx().num_cus * spec_blocks_per_cu, want = (nframes + 3) / 4;
+                const long slots = chip_slots(kern, 256, lds_bytes), want = (nframes + 3) / 4;
+                if (slots < 0) return -1;
                 static const int rounds_env = getenv("LRHIP_SPEC_ROUNDS") ? atoi(getenv("LRHIP_SPEC_ROUNDS")) : -1;      // A/B knob
-                int rounds = rounds_env >= 0 ? rounds_env : 0;      // measured, 2^26 samples, same box: persistent 0.1572 ms, one-shot with 4 / 8 / 16 batches per workgroup 0.1628 / 0.159 / 0.1694
-                if (want <= slots) rounds = 0;
-                unsigned g = rounds > 0 ? (unsigned)((want + rounds - 1) / rounds) : (unsigned)(want < slots ? want : slots);
-                hipLaunchKernelGGL(kern, dim3(g), dim3(256), lds_bytes, ctx().stream, (const float *)in_dev, (float *)out_dev, nframes,
+                const int rounds = persistent_rounds(want, slots, rounds_env);      // measured, 2^26 samples, same box: persistent 0.1572 ms, one-shot with 4 / 8 / 16 batches per workgroup 0.1628 / 0.159 / 0.1694
+                hipLaunchKernelGGL(kern, dim3(persistent_grid(want, slots, rounds)), dim3(256), lds_bytes, ctx().stream, (const float *)in_dev, (float *)out_dev, nframes,
                                    (const float2 *)spec_tables.p, wp, mode, out_scale, shift, rounds);
                 return 0;
             };
@@ -51,17 +43,13 @@ struct FftStage : lrhip_stage {
         unsigned grid = (unsigned)((nframes + fpw - 1) / fpw);
         size_t lds = ((size_t)2 * fpw * N + N / 2) * sizeof(float2);
         const float *w = has_window ? (const float *)window.p : nullptr;
-        if (in_real) {
-            auto kern = fft_frames_kernel<true>;
-            if (lds > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        auto go = [&](auto kern) -> int {
+            if (kernel_allow_lds(kern, lds)) return -1;
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx().stream, (const float *)in_dev, (float *)out_dev, nframes, N, fpw,
                                (const float2 *)tw.p, w, inverse, out_kind, out_scale, shift);
-        } else {
-            auto kern = fft_frames_kernel<false>;
-            if (lds > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx().stream, (const float *)in_dev, (float *)out_dev, nframes, N, fpw,
-                               (const float2 *)tw.p, w, inverse, out_kind, out_scale, shift);
-        }
+            return 0;
+        };
+        if (in_real ? go(fft_frames_kernel<true>) : go(fft_frames_kernel<false>)) return -1;
         LR_LAUNCH_CHECK();
         return (long)n;
     }

@@ -329,3 +329,20 @@ def test_counted_stage_scratch_layouts_on_the_cpu(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
+def test_launch_grid_arithmetic_on_the_cpu(tmp_path):
+    """Every persistent kernel's grid comes from ONE pair of functions, persistent_rounds() and persistent_grid() of luaradio_amd/csrc/launch_prep.h.
+    tools/host_launch_prep_check.hip holds the expressions the launchers spelled out by hand before (both spellings of the rounds gate, the grid with
+    and without rounds), copied as they stood, and compares them over work 0..5000, slots in {1, 255, 256, 768, 2048}, rounds in {0, 1, 2, 4, 8}."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "host_launch_prep_check")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"),
+                        "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "host_launch_prep_check.hip")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
