@@ -306,6 +306,20 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      The reference draws from LuaJIT's sequential math.random, whose values nobody relies on: the
  *                                                      contract is distribution, range and determinism per seed.  Chunking, seek, reset, memory() as
  *                                                      the signal source.
+ *   "arbresampler:type=cf32|f32:phases=P:step=S:taps=h0,h1,..."
+ *                                                      (no block of the reference) a resampler for any rate ratio in [1/16, 16]: a bank of P phases
+ *                                                      (a power of two, 16 .. 256), linearly interpolated between neighbouring phases.  S, a decimal
+ *                                                      uint64 in [2^44, 2^52], is the input samples per output sample in 16.48 fixed point
+ *                                                      (rint(2^48 / ratio)); the taps are a prototype of P T Float32 values at P times the input
+ *                                                      rate, T = 4 .. 512 per phase, P T <= 8192.  G[p][k] = h[k P + p], row P = row 0 one tap later,
+ *                                                      D[p][k] = float(G[p + 1][k] - G[p][k]).  Absolute output m: u = m S (128 bits), i = u >> 48,
+ *                                                      f = u mod 2^48, p = f >> (48 - log2 P), mu = ((f >> (24 - log2 P)) mod 2^24) 2^-24, and
+ *                                                      y[m] = sum_k fmaf(mu, D[p][k], G[p][k]) x[i - k], one fmaf chain per component in ascending k,
+ *                                                      x[j] = 0 for j < 0.  Output m is emitted once input i has arrived: after Q inputs in all
+ *                                                      ceil(Q 2^48 / S) outputs exist, a call returns what is new (possibly 0 samples).  Any chunking
+ *                                                      gives the same bits; max_output(n) = floor(n 2^48 / S) + 2, rate() = S : 2^48 in lowest terms,
+ *                                                      memory() = T - 1, lrhip_stage_seek(n0) continues at output ceil(n0 2^48 / S).  The domain is
+ *                                                      checked before the device is looked at; the stage fuses with nothing.
  * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
  * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time

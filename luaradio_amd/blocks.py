@@ -410,6 +410,68 @@ class PolyphaseSynthesizerBlock(Block):
         return self._execute(np.ascontiguousarray(y).reshape(-1), np.complex64)
 
 
+class ArbitraryResamplerBlock(Block):
+    """Resampler for any rate ratio in [1/16, 16]: a polyphase bank of P phases, linearly interpolated between neighbouring phases (GNU Radio's
+    pfb_arb_resampler, liquid-dsp's resamp).  Not a block of the reference, whose RationalResamplerBlock(L, D) spreads one 128-tap lowpass over L phases.
+    ArbitraryResamplerBlock(ratio[, options]), ratio = output rate / input rate; ComplexFloat32 or Float32.
+    options = {"phases": P, a power of two 16 .. 256 (64); "taps_per_phase": T0, even, 4 .. 32 (16); "taps": a prototype of exactly P * T Float32 values}
+    with T = 2 * ceil(T0 / (2 * min(1, ratio))) taps per phase - the filter is stretched when decimating - and P * T <= 8192.
+    The default prototype is P * firwin_lowpass(P * T, min(1, ratio) / P).  The position of output m is m * step in 16.48 fixed point,
+    step = rint(2^48 / ratio): the ratio in effect is effective_ratio = 2^48 / step, and the output is bit-identical however the stream is cut
+    (luaradio_amd/csrc/kernels_arbresample.h has the arithmetic).  A call returns the outputs whose newest input has arrived, possibly none."""
+    name = "ArbitraryResamplerBlock"
+
+    @staticmethod
+    def taps_per_phase(ratio, t0=16):
+        """T: T0 stretched by the decimation, kept even"""
+        return 2 * math.ceil(t0 / (2 * min(1.0, ratio)))
+
+    def instantiate(self, ratio, options=None):
+        assert ratio is not None, "Missing argument #1 (ratio)"
+        options = options or {}
+        ratio = float(ratio)
+        if not (math.isfinite(ratio) and 1 / 16 <= ratio <= 16):
+            raise ValueError("arbresampler: ratio must be a finite number in [1/16, 16], got %r" % ratio)
+        self.phases = options.get("phases", 64)
+        if self.phases not in (16, 32, 64, 128, 256):
+            raise ValueError("arbresampler: phases must be a power of two in [16, 256], got %r" % (self.phases,))
+        t0 = options.get("taps_per_phase", 16)
+        if not (isinstance(t0, (int, np.integer)) and 4 <= t0 <= 32 and t0 % 2 == 0):
+            raise ValueError("arbresampler: taps_per_phase must be an even integer in [4, 32], got %r" % (t0,))
+        self.ratio = ratio
+        self.num_taps = self.taps_per_phase(ratio, int(t0))
+        P, T = self.phases, self.num_taps
+        if P * T > 8192:
+            raise ValueError("arbresampler: phases * taps per phase must not exceed 8192 (got phases = %d with %d taps per phase at ratio %r): "
+                             "use fewer phases" % (P, T, ratio))
+        self.step = int(np.rint(2.0 ** 48 / ratio))
+        self.effective_ratio = 2.0 ** 48 / self.step
+        taps = options.get("taps")
+        if taps is None:
+            # RationalResamplerBlock's convention, gain P: designed in double, rounded once to Float32
+            taps = P * np.asarray(filter_utils.firwin_lowpass(P * T, min(1.0, ratio) / P), np.float64)
+        self.taps = types.Float32.vector_from_array(taps)
+        if len(self.taps) != P * T:
+            raise ValueError("arbresampler: taps must hold exactly phases * taps per phase = %d * %d values, got %d" % (P, T, len(self.taps)))
+        self.add_type_signature([Input("in", types.ComplexFloat32)], [Output("out", types.ComplexFloat32)])
+        self.add_type_signature([Input("in", types.Float32)], [Output("out", types.Float32)])
+
+    def get_rate(self):
+        return Block.get_rate(self) * self.effective_ratio
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; %.9g gives every Float32 tap back exactly"""
+        return "arbresampler:type=%s:phases=%d:step=%d:taps=%s" % ("cf32" if self.get_input_type() is types.ComplexFloat32 else "f32", self.phases, self.step,
+                                                                  ",".join("%.9g" % float(v) for v in np.asarray(self.taps, np.float32)))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, int(self.get_input_type() is types.ComplexFloat32)),
+                        "Creating lrhip arbresampler object")
+
+    def process(self, x):
+        return self._execute(x, self.get_output_type().dtype)
+
+
 class _UnaryBlock(Block):
     """One-input element-wise blocks with fixed types."""
     _op, _in, _out = "", types.ComplexFloat32, types.Float32
