@@ -271,6 +271,25 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      no read-back.  rate() = b : P, memory() = 0; lrhip_stage_seek(n0) needs n0 % b == 0 (the bits another
  *                                                      partition holds back are unknown) and fails otherwise, leaving the stage as it was.
  *   "qam:period=P:bits=b:msb=0|1:table=re0,im0,re1,im1,..."  (quadratureamplitudemodulator.lua:69-99) Bit -> ComplexFloat32, otherwise as "pam".
+ *   "pamdemod:period=P:offset=o:bits=b:msb=0|1:soft=0|1:weight=w:grid=1:table=a0,a1,..."  (no block of the reference: the inverse of "pam") Float32 ->
+ *                                                      Bit, or -> Float32 with soft=1.  Symbol s of the stream is decided on input sample s P + offset
+ *                                                      (o in 0 .. P - 1) against the 2^b table entries, which the caller has already scaled to the received
+ *                                                      amplitudes.  Float32 arithmetic, each operation rounded on its own: d_v = fl(dr dr), dr = x - a_v.
+ *                                                      Hard: the first v with the smallest d_v (best = +inf, v taken when d_v < best; a NaN or infinite sample
+ *                                                      decides 0), written as b Bit bytes, positions b-1 .. 0 of v with msb=1, else 0 .. b-1.  Soft: in the same
+ *                                                      order llr_k = fl(fl(m1_k - m0_k) w), m0_k / m1_k the smallest d_v over the entries with bit k clear / set
+ *                                                      (the same comparison from +inf), w a finite Float32 above 0; positive = bit 0.  All keys are required;
+ *                                                      P, b and the table's text as "pam".  The only state is the absolute input position: a call emits b
+ *                                                      outputs per symbol whose sample it delivers (max_output: (n / P + 1) b; possibly none), no read-back,
+ *                                                      any chunking gives the same bytes; lrhip_stage_seek(n0) takes any n0 and continues at symbol
+ *                                                      ceil((n0 - o) / P) (0 while n0 <= o).  rate() = P : b, memory() = 0.  Fuses with nothing.
+ *   "qamdemod:period=P:offset=o:bits=b:msb=0|1:soft=0|1:weight=w:grid=qb|-1:table=re0,im0,re1,im1,..."  ComplexFloat32 -> Bit / Float32, as "pamdemod"
+ *                                                      with d_v = fl(fl(dr dr) + fl(di di)).  grid=-1: the search over all entries, b <= 12.  grid=qb, 0 <= qb <= b:
+ *                                                      the caller states that table[v] = (I[v >> qb], Q[v & (2^qb - 1)]) bit for bit for every v (checked; b <= 16)
+ *                                                      and each axis is decided on its own by the same rule on fl(dr dr) and fl(di di), the two indices joined:
+ *                                                      differs from grid=-1 only where two candidates differ before the final addition and coincide after it, or
+ *                                                      one component is NaN.  Soft output is the same Float32 in both forms (m = fl(min_i a_i + min_q b_q) with
+ *                                                      the bit's axis restricted to its half).
  *   "pfbsynthesizer:channels=K:oversample=R:taps=g0,g1,..."  (no block of the reference: the inverse of lrhip_pfb_oversampled_create) the K-channel synthesis
  *                                                      filterbank in its polyphase + FFT form: K chains Upsampler(D) -> FIR(g) -> FrequencyTranslator(+c / K),
  *                                                      D = K / R, summed, with zero history:  xhat[n] = sum_c exp(+j 2 pi c n / K) sum_m g[n - m D] Y[m, c].

@@ -1159,10 +1159,11 @@ def qam_constellation(points):
     return table
 
 
-class _ModulatorBlock(Block):
-    _op, _out, _count_name, _table_option = None, None, None, None
+class _SymbolMapBlock(Block):
+    """what the modulators and the demodulators share: the arguments, their assertions, and the symbol table"""
+    _op, _sample, _count_name, _table_option = None, None, None, None
 
-    def instantiate(self, symbol_rate, sample_rate, count, options=None):
+    def _symbol_arguments(self, symbol_rate, sample_rate, count, options):
         assert symbol_rate is not None, "Missing argument #1 (symbol_rate)"
         assert sample_rate is not None, "Missing argument #2 (sample_rate)"
         assert count is not None, "Missing argument #3 (%s)" % self._count_name.lower()
@@ -1171,21 +1172,29 @@ class _ModulatorBlock(Block):
         self.symbol_period = _symbol_period(symbol_rate, sample_rate)
         msb_first = self.options.get("msb_first")
         self.msb_first = True if msb_first is None else bool(msb_first)
-        self.add_type_signature([Input("in", types.Bit)], [Output("out", self._out)])
 
     def _default_table(self):
         raise NotImplementedError
 
     def table(self):
-        """the symbol table as the output type's vector, indexed by symbol value"""
+        """the symbol table as the sample type's vector, indexed by symbol value"""
         custom = self.options.get(self._table_option)
         if custom is None:
             return self._default_table()
         entries = _symbol_table(custom, 1 << self.symbol_bits, self._table_option)
-        if self._out is types.ComplexFloat32:
+        if self._sample is types.ComplexFloat32:
             entries = [complex(*e) if isinstance(e, (list, tuple)) else complex(e) for e in entries]
             return np.array([complex(np.float32(e.real), np.float32(e.imag)) for e in entries], np.complex64)
         return np.array([np.float32(e) for e in entries], np.float32)
+
+
+class _ModulatorBlock(_SymbolMapBlock):
+    _out = None
+    _sample = property(lambda self: self._out)
+
+    def instantiate(self, symbol_rate, sample_rate, count, options=None):
+        self._symbol_arguments(symbol_rate, sample_rate, count, options)
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", self._out)])
 
     def op(self):
         values = self.table().view(np.float32)
@@ -1224,6 +1233,112 @@ class QuadratureAmplitudeModulatorBlock(_ModulatorBlock):
 
     def instantiate(self, symbol_rate, sample_rate, points, options=None):
         _ModulatorBlock.instantiate(self, symbol_rate, sample_rate, points, options)
+        self.points = int(points)
+
+    def _default_table(self):
+        return qam_constellation(self.points)
+
+
+# ---- the sample -> Bit / LLR blocks (luaradio_amd/csrc/stage_demodulator.h)
+DEMODULATOR_GENERAL_MAX_BITS = 12           # DEM_GENERAL_MAX_BITS: a table that is no grid is searched from LDS, 2^12 entries at most
+
+
+def scaled_symbol_table(table, scale):
+    """the received constellation scale * table: per component Float32(double(entry) * scale), rounded once"""
+    values = (np.ascontiguousarray(table).view(np.float32).astype(np.float64) * float(scale)).astype(np.float32)
+    return values.view(table.dtype)
+
+
+def constellation_grid_bits(table):
+    """the smallest qb in 0 .. b with table[v] == (I[v >> qb], Q[v & (2^qb - 1)]) bit for bit for every symbol value v, or None: the demodulator
+    then decides each axis on its own (stage_demodulator.h).  Every default qam_constellation is such a grid."""
+    table = np.ascontiguousarray(table, np.complex64)
+    words = table.view(np.uint32).reshape(-1, 2)
+    v = np.arange(len(table))
+    for qb in range(len(table).bit_length()):
+        if np.array_equal(words[:, 0], words[v >> qb << qb, 0]) and np.array_equal(words[:, 1], words[v & ((1 << qb) - 1), 1]):
+            return qb
+    return None
+
+
+class _DemodulatorBlock(_SymbolMapBlock):
+    def instantiate(self, symbol_rate, sample_rate, count, options=None):
+        self._symbol_arguments(symbol_rate, sample_rate, count, options)
+        offset = self.options.get("offset", 0)
+        if isinstance(offset, bool) or int(offset) != offset or not 0 <= offset < self.symbol_period:
+            raise ValueError("offset = %r is not an integer in 0 .. %d (the symbol period less one)" % (offset, self.symbol_period - 1))
+        self.offset = int(offset)
+        self.scale = float(self.options.get("scale", 1.0))
+        if not math.isfinite(self.scale):
+            raise ValueError("scale = %r is not finite" % self.scale)
+        self.soft = bool(self.options.get("soft", False))
+        noise_variance = self.options.get("noise_variance")
+        if noise_variance is not None and not self.soft:
+            raise ValueError("noise_variance is the weight of the soft decisions: it needs soft = True")
+        self.noise_variance = 1.0 if noise_variance is None else float(noise_variance)
+        if not self.noise_variance > 0:
+            raise ValueError("noise_variance = %r is not greater than 0" % self.noise_variance)
+        with np.errstate(over="ignore"):
+            self.weight = np.float32(1.0 / self.noise_variance)
+        if not (np.isfinite(self.weight) and self.weight > 0):
+            raise ValueError("noise_variance = %r gives no finite Float32 weight above 0" % self.noise_variance)
+        self.add_type_signature([Input("in", self._sample)], [Output("out", types.Float32 if self.soft else types.Bit)])
+
+    def received_table(self):
+        """scale * table, what the stage compares the samples with"""
+        return scaled_symbol_table(self.table(), self.scale)
+
+    def grid(self):
+        """the op string's grid field: 1 for the one axis of pam; for qam the low bits of the second axis, -1 for a table that is no grid"""
+        if self._sample is types.Float32:
+            return 1
+        qb = constellation_grid_bits(self.received_table())
+        if qb is None and self.symbol_bits > DEMODULATOR_GENERAL_MAX_BITS:
+            raise ValueError("%s = %d: a %s that is no grid is limited to 2^%d entries" % (self._count_name, 1 << self.symbol_bits, self._table_option,
+                                                                                          DEMODULATOR_GENERAL_MAX_BITS))
+        return -1 if qb is None else qb
+
+    def op(self, grid=None):
+        """grid = -1 runs a grid-shaped table through the general search (the tests compare the two forms that way)"""
+        values = self.received_table().view(np.float32)
+        return "%s:period=%d:offset=%d:bits=%d:msb=%d:soft=%d:weight=%.9g:grid=%d:table=%s" % (
+            self._op, self.symbol_period, self.offset, self.symbol_bits, int(self.msb_first), int(self.soft), float(self.weight),
+            self.grid() if grid is None else grid, ",".join("%.9g" % float(v) for v in values))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self._op)
+
+    def process(self, x):
+        return self._execute(x, np.float32 if self.soft else np.uint8)
+
+
+class PulseAmplitudeDemodulatorBlock(_DemodulatorBlock):
+    """PulseAmplitudeDemodulatorBlock(symbol_rate, sample_rate, levels[, options]): Float32 -> Bit, the inverse of PulseAmplitudeModulatorBlock (no
+    block of the reference).  Symbol s is decided on input sample s P + offset, P = floor(sample_rate / symbol_rate), by the nearest amplitude (ties:
+    the lowest symbol value) and leaves as log2(levels) bits.  options: msb_first, amplitudes (as the modulator's); offset (0 .. P - 1, default 0);
+    scale (default 1.0: the received amplitudes are scale * amplitudes); soft (default False; True: Float32 max-log LLRs in place of the bits, in the same
+    order, positive = bit 0); noise_variance (default 1.0, with soft only: the LLRs are weighted by 1 / noise_variance).  As the modulators, the block
+    does not change the rate it reports."""
+    name = "PulseAmplitudeDemodulatorBlock"
+    _op, _sample, _count_name, _table_option = "pamdemod", types.Float32, "Levels", "amplitudes"
+
+    def instantiate(self, symbol_rate, sample_rate, levels, options=None):
+        _DemodulatorBlock.instantiate(self, symbol_rate, sample_rate, levels, options)
+        self.levels = int(levels)
+
+    def _default_table(self):
+        return pam_amplitudes(self.levels)
+
+
+class QuadratureAmplitudeDemodulatorBlock(_DemodulatorBlock):
+    """QuadratureAmplitudeDemodulatorBlock(symbol_rate, sample_rate, points[, options]): ComplexFloat32 -> Bit (Float32 with soft), as the pulse
+    amplitude demodulator with a constellation (option constellation, as the modulator's).  A constellation that is a grid of two axes - every default
+    one - is decided per axis; any other one of up to 2^12 points by a search over all points."""
+    name = "QuadratureAmplitudeDemodulatorBlock"
+    _op, _sample, _count_name, _table_option = "qamdemod", types.ComplexFloat32, "Points", "constellation"
+
+    def instantiate(self, symbol_rate, sample_rate, points, options=None):
+        _DemodulatorBlock.instantiate(self, symbol_rate, sample_rate, points, options)
         self.points = int(points)
 
     def _default_table(self):

@@ -35,6 +35,7 @@
 #include "kernels_pocsagframer.h"
 #include "kernels_phasecorr.h"
 #include "kernels_modulator.h"
+#include "kernels_demodulator.h"
 #include "kernels_pll.h"
 #include "kernels_interleave.h"
 #include "kernels_source.h"
@@ -70,6 +71,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_preamble.h"
 #include "stage_framers.h"
 #include "stage_modulator.h"
+#include "stage_demodulator.h"
 #include "stage_pfbsynth.h"
 #include "stage_interleave.h"
 #include "stage_source.h"
@@ -333,6 +335,7 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         {"zerocrossingclockrecovery", zc_create}, {"clocksampler", zc_create}, {"slicer", slicer_create}, {"differentialdecoder", diffdec_create},
         {"binaryphasecorrector", phasecorr_create}, {"pll", pll_create}, {"preamblesampler", preamblesampler_create},
         {"manchesterdecoder", manchesterdecoder_create}, {"pam", modulator_create}, {"qam", modulator_create},
+        {"pamdemod", demodulator_create}, {"qamdemod", demodulator_create},
         {"pfbsynthesizer", pfb_synthesizer_create}, {"interleave", port_stage_create}, {"deinterleave", port_stage_create},
         {"wavpack", port_stage_create}, {"wavunpack", port_stage_create}, {"signalsource", source_create}, {"uniformrandomsource", source_create},
         {"arbresampler", arbresampler_create},

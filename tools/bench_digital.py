@@ -5,7 +5,7 @@ ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the 
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
 (4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
 PAM / QAM modulators, of the SCM / SCM+ / IDM framers, of the AX.25 / POCSAG framers and of the Varicode decoder instead (modulator_rows,
-ert_framer_rows, packet_framer_rows, varicode_rows)."""
+ert_framer_rows, packet_framer_rows, varicode_rows); --demodulators prints the rows of the PAM / QAM demodulators (demodulator_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -22,13 +22,16 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--modulators", action="store_true", help="only the PAM / QAM modulator rows (profiles/modulator_table.jsonl)")
+    ap.add_argument("--demodulators", action="store_true", help="only the PAM / QAM demodulator rows (profiles/demodulator_table.jsonl)")
     ap.add_argument("--ert-framers", action="store_true", help="only the SCM / SCM+ / IDM framer rows (profiles/ert_framer_table.jsonl)")
     ap.add_argument("--packet-framers", action="store_true", help="only the AX.25 / POCSAG framer rows (profiles/packet_framer_table.jsonl)")
     ap.add_argument("--varicode", action="store_true", help="only the Varicode decoder rows (profiles/varicode_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --ert-framers / --packet-framers / --varicode: append the rows to this file as well")
+    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode: append the rows to this file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
+    if args.demodulators:
+        return demodulator_rows(args)
     if args.ert_framers:
         return ert_framer_rows(args)
     if args.packet_framers:
@@ -174,6 +177,73 @@ def modulator_rows(args):
     cap = chain.max_output(bits)
     ms = [timed(lambda: chain.process_device(x.data_ptr(), bits, y.data_ptr(), cap)) for _ in range(3)]
     emit({"row": "QAM(4) P=8 -> RRC(129)", "outputs": m_out, "ms": ms, "launches": chain.last_launches, "GS/s": round(m_out / min(ms) / 1e6, 2)})
+
+
+def demodulator_rows(args):
+    """The stand-alone demodulators on 2^24 resident symbols, one sample per symbol (the kernels read 4 or 8 bytes and write b bytes, or 4 b with soft,
+    per symbol) - each next to a read-only pass over the same input bytes (torch's sum: a yardstick for the load stream, not one of the library's
+    kernels), the two alternating three times.  QAM-256 runs in its grid form and forced through the general search (grid=-1).  A record, not an
+    acceptance criterion.  --out appends the rows to a file (profiles/demodulator_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import _lib, types
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+    n = 1 << 24
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    psk8 = [complex(np.cos(2 * np.pi * k / 8), np.sin(2 * np.pi * k / 8)) for k in range(8)]
+    rows = [("QAM-16 hard", lr.QuadratureAmplitudeDemodulatorBlock, 16, {}, False),
+            ("QAM-256 hard, grid", lr.QuadratureAmplitudeDemodulatorBlock, 256, {}, False),
+            ("QAM-256 hard, general", lr.QuadratureAmplitudeDemodulatorBlock, 256, {}, True),
+            ("QAM-256 soft, grid", lr.QuadratureAmplitudeDemodulatorBlock, 256, {"soft": True}, False),
+            ("QAM-256 soft, general", lr.QuadratureAmplitudeDemodulatorBlock, 256, {"soft": True}, True),
+            ("8-PSK hard (custom table)", lr.QuadratureAmplitudeDemodulatorBlock, 8, {"constellation": psk8}, False),
+            ("PAM-4 hard", lr.PulseAmplitudeDemodulatorBlock, 4, {}, False)]
+    for name, cls, count, options, general in rows:
+        blk = cls(1.0, 1.0, count, options)
+        blk.rate = 1.0
+        cplx = cls is lr.QuadratureAmplitudeDemodulatorBlock
+        blk.differentiate([types.ComplexFloat32 if cplx else types.Float32])
+        if general:
+            blk._set_stage(_lib.load().lrhip_unary_create(blk.op(grid=-1).encode(), 0.0, 0.0, 0, 0), "Creating a qamdemod stage with grid=-1")
+        else:
+            blk.initialize()
+        table = blk.received_table()
+        words = 2 if cplx else 1
+        noise = 0.1 * rng.standard_normal(n * words).astype(np.float32)
+        x = torch.from_numpy(table[rng.integers(0, count, n)].view(np.float32) + noise).cuda()
+        bits = count.bit_length() - 1
+        out_size = 4 if blk.soft else 1
+        cap = blk.max_output(n)
+        y = torch.empty(cap * out_size + 64, dtype=torch.uint8, device="cuda")
+        ms, ms_read = [], []
+        for _ in range(3):
+            blk.reset()
+            ms.append(timed(lambda: blk.process_device(x.data_ptr(), n, y.data_ptr(), cap)))
+            ms_read.append(timed(lambda: x.sum()))
+        row = {"row": name, "symbols": n, "op": blk.op(grid=-1 if general else None).split(":table=")[0], "ms": ms, "read_only_ms": ms_read,
+               "share_of_read_only": round(min(ms_read) / min(ms), 3), "Gsymbol/s": round(n / min(ms) / 1e6, 2),
+               "roof_fraction": round(n * (4 * words + bits * out_size) / (min(ms) * 1e-3) / 8e12, 3)}
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
 
 def ert_framer_rows(args):
