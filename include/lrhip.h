@@ -339,6 +339,27 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      gives the same bits; max_output(n) = floor(n 2^48 / S) + 2, rate() = S : 2^48 in lowest terms,
  *                                                      memory() = T - 1, lrhip_stage_seek(n0) continues at output ceil(n0 2^48 / S).  The domain is
  *                                                      checked before the device is looked at; the stage fuses with nothing.
+ *   "convenc:k=K:polys=g0,g1,..."                      (no block of the reference) Bit -> Bit, a rate-1/n convolutional encoder: K = 3 .. 9, n = 2 .. 4
+ *                                                      polynomials as OCTAL text ("polys=171,133"), each below 2^K, bit K - 1 multiplying the current
+ *                                                      input bit; at least one polynomial has bit K - 1 and one has bit 0.  r = (u << (K - 1)) | (r >> 1)
+ *                                                      from r = 0 at bit 0 of the stream (bit 0 of each input byte is read), out[n t + j] =
+ *                                                      parity(r & g_j).  max_output(m) = n m, rate() = 1 : n, memory() = K - 1, lrhip_stage_seek(n0)
+ *                                                      takes any n0 and continues at output n n0.
+ *   "viterbi:k=K:polys=g0,g1,...:input=llr|bit:scale=s:block=D:depth=L"
+ *                                                      (no block of the reference) the windowed Viterbi decoder of that code.  input=llr: Float32 LLRs,
+ *                                                      positive = 0, each quantised once to q = clamp(rintf(float(llr s)), -127, 127), NaN -> 0;
+ *                                                      input=bit: q = 127 (1 - 2 b).  s a finite Float32 above 0, D = 64 .. 2048, L = K - 1 .. 256,
+ *                                                      (D + 2 L) 2^(K - 1) / 8 <= 65536.  All keys are required.  Step t reads the inputs n t .. n t + n - 1
+ *                                                      of the stream; window w decodes the bits [w D, (w + 1) D) from the steps max(0, w D - L) ..
+ *                                                      (w + 1) D + L - 1 in int32 (csrc/kernels_viterbi.h has the trellis and the tie rules), starting
+ *                                                      from state 0 at step 0 and from equal metrics elsewhere, and tracing back from the best final
+ *                                                      state.  After Q inputs, E = floor(Q / n), floor((E - L) / D) windows are out (none while E < L):
+ *                                                      a call returns the windows it completes, possibly none, from the lengths alone.  There is no
+ *                                                      flush: the last fewer than D + L bits of a stream never leave.  Any chunking gives the same
+ *                                                      bytes; max_output(N) = D ceil(ceil(N / n) / D), rate() = n : 1, memory() = n (D + 2 L) - 1;
+ *                                                      lrhip_stage_seek(n0) takes any n0, continues at bit D floor((floor(n0 / n) - L) / D) and counts the
+ *                                                      inputs in front of n0 as erasures.  Both stages check their domain before the device is
+ *                                                      looked at and fuse with nothing.
  * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
  * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time

@@ -20,7 +20,8 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      BinaryPhaseCorrectorBlock, PreambleSamplerBlock, ManchesterDecoderBlock, VaricodeDecoderBlock, RDSFramerBlock,
                      SCMFramerBlock, SCMPlusFramerBlock, IDMFramerBlock, AX25FramerBlock, POCSAGFramerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock, InterleaveBlock, DeinterleaveBlock,
-                     ArbitraryResamplerBlock, PulseAmplitudeDemodulatorBlock, QuadratureAmplitudeDemodulatorBlock)
+                     ArbitraryResamplerBlock, PulseAmplitudeDemodulatorBlock, QuadratureAmplitudeDemodulatorBlock,
+                     ConvolutionalEncoderBlock, ViterbiDecoderBlock)
 from .sources import (IQFileSource, RealFileSource, IQFileSink, RealFileSink, WAVFileSink, WAVFileSource, wav_header, parse_wav_header,  # noqa: F401
                       SignalSource, UniformRandomSource)
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401

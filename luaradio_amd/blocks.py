@@ -1345,6 +1345,125 @@ class QuadratureAmplitudeDemodulatorBlock(_DemodulatorBlock):
         return qam_constellation(self.points)
 
 
+# ---- forward error correction (luaradio_amd/csrc/stage_viterbi.h): a rate-1/n convolutional code and its windowed Viterbi decoder
+def _is_integer(v):
+    """an int or a numpy integer, and no bool"""
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_convolutional_code(who, constraint_length, polynomials):
+    """the checks both blocks share; the library makes them again on the op string.  Returns (K, [g_0, ...])"""
+    K = constraint_length
+    if not (_is_integer(K) and 3 <= K <= 9):
+        raise ValueError("%s: constraint length must be 3 .. 9 (got %r)" % (who, K))
+    try:
+        polys = list(polynomials)
+    except TypeError:
+        raise ValueError("%s: polynomials must be a list of integers (got %r)" % (who, polynomials))
+    for g in polys:
+        if not _is_integer(g):
+            raise ValueError("%s: polynomials must be integers (got %r)" % (who, g))
+    polys = [int(g) for g in polys]
+    if not 2 <= len(polys) <= 4:
+        raise ValueError("%s: the number of polynomials must be 2 .. 4 (got %d)" % (who, len(polys)))
+    for g in polys:
+        if g < 0 or g >> K:
+            raise ValueError("%s: polynomial %s (octal) has bits at or above the constraint length %d" % (who, ("%o" % g) if g >= 0 else g, K))
+    text = ",".join("%o" % g for g in polys)
+    if not any((g >> (K - 1)) & 1 for g in polys):
+        raise ValueError("%s: no polynomial of %s has bit %d set: the current input bit reaches no output" % (who, text, K - 1))
+    if not any(g & 1 for g in polys):
+        raise ValueError("%s: no polynomial of %s has bit 0 set: the constraint length is below %d" % (who, text, K))
+    return int(K), polys
+
+
+class ConvolutionalEncoderBlock(Block):
+    """ConvolutionalEncoderBlock(constraint_length, polynomials): Bit -> Bit, n = len(polynomials) output bits per input bit.  Not a block of the
+    reference.  K = constraint_length is 3 .. 9, n is 2 .. 4, and the polynomials are integers in the usual octal notation, bit K - 1 multiplying
+    the current input bit: ConvolutionalEncoderBlock(7, [0o171, 0o133]) is the code of DVB-S, 802.11a and CCSDS.  The register starts at zero at
+    bit 0 of the stream; r = (u << (K - 1)) | (r >> 1), out[n t + j] = parity(r & g_j)."""
+    name = "ConvolutionalEncoderBlock"
+
+    def instantiate(self, constraint_length, polynomials):
+        assert constraint_length is not None, "Missing argument #1 (constraint_length)"
+        assert polynomials is not None, "Missing argument #2 (polynomials)"
+        self.constraint_length, self.polynomials = check_convolutional_code("convenc", constraint_length, polynomials)
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.Bit)])
+
+    def get_rate(self):
+        return Block.get_rate(self) * len(self.polynomials)
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; the polynomials are octal text"""
+        return "convenc:k=%d:polys=%s" % (self.constraint_length, ",".join("%o" % g for g in self.polynomials))
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip convenc object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
+class ViterbiDecoderBlock(Block):
+    """ViterbiDecoderBlock(constraint_length, polynomials[, options]): Float32 LLRs -> Bit, or Bit -> Bit; the decoder of ConvolutionalEncoderBlock.
+    Not a block of the reference.
+    options = {"soft": True - the input is Float32 LLRs in the demodulators' convention, POSITIVE MEANS 0; False - Bit, a bit b counting as the
+               saturated value 127 (1 - 2 b);
+               "scale": 8.0 - an LLR is quantised once to clamp(rint(llr * scale), -127, 127), NaN to 0 (an erasure);
+               "block": D = 512 decoded bits per window, 64 .. 2048;
+               "depth": L = 8 (K - 1) steps, K - 1 .. 256: the acquisition length in front of a window and the traceback tail behind it}
+    with (D + 2 L) 2^(K - 1) / 8 <= 65536 bytes of decisions per window.
+    A sliding-window decoder on absolute step indices: window w decodes the bits [w D, (w + 1) D) from the steps max(0, w D - L) ..
+    (w + 1) D + L - 1 of the stream, so the output is a function of the stream alone - any chunking, reset, seek or time partition gives the same
+    bits - and a call returns the windows its inputs complete, possibly none.  THERE IS NO FLUSH: the last fewer than D + L bits of a stream are
+    never emitted; pad the stream with n (D + L) zero LLRs (erasures) to get them.  luaradio_amd/csrc/kernels_viterbi.h has the arithmetic."""
+    name = "ViterbiDecoderBlock"
+
+    def instantiate(self, constraint_length, polynomials, options=None):
+        assert constraint_length is not None, "Missing argument #1 (constraint_length)"
+        assert polynomials is not None, "Missing argument #2 (polynomials)"
+        options = options or {}
+        K, self.polynomials = check_convolutional_code("viterbi", constraint_length, polynomials)
+        self.constraint_length = K
+        self.soft = bool(options.get("soft", True))
+        scale = options.get("scale", 8.0)
+        try:
+            self.scale = np.float32(scale)
+        except (TypeError, ValueError):
+            raise ValueError("viterbi: scale must be a finite Float32 above 0 (got %r)" % (scale,))
+        if not (np.isfinite(self.scale) and self.scale > 0):
+            raise ValueError("viterbi: scale must be a finite Float32 above 0 (got %r)" % (scale,))
+        self.block = options.get("block", 512)
+        if not (_is_integer(self.block) and 64 <= self.block <= 2048):
+            raise ValueError("viterbi: block must be 64 .. 2048 decoded bits (got %r)" % (self.block,))
+        self.depth = options.get("depth", 8 * (K - 1))
+        if not (_is_integer(self.depth) and K - 1 <= self.depth <= 256):
+            raise ValueError("viterbi: depth must be %d .. 256 steps (got %r)" % (K - 1, self.depth))
+        nbytes = (self.block + 2 * self.depth) * (1 << (K - 1)) // 8
+        if nbytes > 65536:
+            raise ValueError("viterbi: the decision words of one window, (block + 2 depth) * 2^(k - 1) / 8 = %d bytes, exceed 65536: "
+                             "use a smaller block or depth" % nbytes)
+        self.add_type_signature([Input("in", types.Float32 if self.soft else types.Bit)], [Output("out", types.Bit)])
+
+    def get_rate(self):
+        return Block.get_rate(self) / len(self.polynomials)
+
+    def memory(self):
+        """inputs after which a decoder started by seek() emits what the uninterrupted stream would"""
+        return len(self.polynomials) * (self.block + 2 * self.depth) - 1
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; the polynomials are octal text, %.9g gives the Float32 scale back exactly"""
+        return "viterbi:k=%d:polys=%s:input=%s:scale=%.9g:block=%d:depth=%d" % (self.constraint_length, ",".join("%o" % g for g in self.polynomials),
+                                                                            "llr" if self.soft else "bit", float(self.scale), self.block, self.depth)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip viterbi object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
 # ---- many-ported blocks (luaradio_amd/csrc/stage_interleave.h).  The side of the call with several ports travels as a port table
 # (_lib.port_table), the stages run through lrhip_stage_execute_device alone.
 MAX_CHANNELS = _lib.MAX_PORTS

@@ -5,7 +5,8 @@ ComplexFloat32 samples next to a copy of the same buffer (16 B/sample); and the 
 tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches per call, and the fraction of 8 TB/s on the algorithmic bytes
 (4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
 PAM / QAM modulators, of the SCM / SCM+ / IDM framers, of the AX.25 / POCSAG framers and of the Varicode decoder instead (modulator_rows,
-ert_framer_rows, packet_framer_rows, varicode_rows); --demodulators prints the rows of the PAM / QAM demodulators (demodulator_rows)."""
+ert_framer_rows, packet_framer_rows, varicode_rows); --demodulators prints the rows of the PAM / QAM demodulators (demodulator_rows); --fec those of
+the convolutional encoder and the Viterbi decoder (fec_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -26,7 +27,8 @@ def main():
     ap.add_argument("--ert-framers", action="store_true", help="only the SCM / SCM+ / IDM framer rows (profiles/ert_framer_table.jsonl)")
     ap.add_argument("--packet-framers", action="store_true", help="only the AX.25 / POCSAG framer rows (profiles/packet_framer_table.jsonl)")
     ap.add_argument("--varicode", action="store_true", help="only the Varicode decoder rows (profiles/varicode_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode: append the rows to this file as well")
+    ap.add_argument("--fec", action="store_true", help="only the convolutional encoder / Viterbi decoder rows (profiles/fec_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode / --fec: append the rows to this file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
@@ -38,6 +40,8 @@ def main():
         return packet_framer_rows(args)
     if args.varicode:
         return varicode_rows(args)
+    if args.fec:
+        return fec_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -239,6 +243,72 @@ def demodulator_rows(args):
         row = {"row": name, "symbols": n, "op": blk.op(grid=-1 if general else None).split(":table=")[0], "ms": ms, "read_only_ms": ms_read,
                "share_of_read_only": round(min(ms_read) / min(ms), 3), "Gsymbol/s": round(n / min(ms) / 1e6, 2),
                "roof_fraction": round(n * (4 * words + bits * out_size) / (min(ms) * 1e-3) / 8e12, 3)}
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
+
+
+def fec_rows(args):
+    """ConvolutionalEncoderBlock and ViterbiDecoderBlock on resident vectors, 2^24 decoded (or message) bits per call: the encoder, the K = 7
+    (171, 133) soft decoder at its default block of 512 and at 256 and 1024 (the LDS a window takes, and with it the resident waves, goes with the
+    block), the same on hard bits, and the K = 9 (561, 753) soft decoder - each next to a read-only pass over the same input bytes (torch's sum, as in
+    demodulator_rows), the two alternating three times.  Successive calls continue one stream, so every timed call decodes exactly 2^24 / D windows.
+    A record, not an acceptance criterion.  --out appends the rows to a file (profiles/fec_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(1)
+    nbits = 1 << 24
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    k7, k9 = [0o171, 0o133], [0o561, 0o753]
+    rows = [("ConvolutionalEncoder K=7", lr.ConvolutionalEncoderBlock, (7, k7), types.Bit),
+            ("Viterbi K=7 soft, block 512", lr.ViterbiDecoderBlock, (7, k7, {}), types.Float32),
+            ("Viterbi K=7 soft, block 256", lr.ViterbiDecoderBlock, (7, k7, {"block": 256}), types.Float32),
+            ("Viterbi K=7 soft, block 1024", lr.ViterbiDecoderBlock, (7, k7, {"block": 1024}), types.Float32),
+            ("Viterbi K=7 hard, block 512", lr.ViterbiDecoderBlock, (7, k7, {"soft": False}), types.Bit),
+            ("Viterbi K=9 soft, block 512", lr.ViterbiDecoderBlock, (9, k9, {}), types.Float32),
+            ("Viterbi K=9 soft, block 256", lr.ViterbiDecoderBlock, (9, k9, {"block": 256}), types.Float32)]
+    for name, cls, arguments, in_type in rows:
+        blk = cls(*arguments)
+        blk.rate = 1.0
+        blk.differentiate([in_type])
+        blk.initialize()
+        decoder = cls is lr.ViterbiDecoderBlock
+        n_in = nbits * len(blk.polynomials) if decoder else nbits
+        if in_type is types.Float32:
+            x = torch.from_numpy((2.0 * rng.standard_normal(n_in)).astype(np.float32)).cuda()
+        else:
+            x = torch.from_numpy(rng.integers(0, 2, n_in).astype(np.uint8)).cuda()
+        cap = blk.max_output(n_in)
+        y = torch.empty(cap + 64, dtype=torch.uint8, device="cuda")
+        ms, ms_read = [], []
+        for _ in range(3):
+            blk.reset()
+            ms.append(timed(lambda: blk.process_device(x.data_ptr(), n_in, y.data_ptr(), cap)))
+            ms_read.append(timed(lambda: x.sum()))
+        row = {"row": name, "bits": nbits, "op": blk.op(), "ms": ms, "read_only_ms": ms_read, "share_of_read_only": round(min(ms_read) / min(ms), 3),
+               "Gbit/s": round(nbits / min(ms) / 1e6, 2)}
+        if decoder:
+            K, steps = blk.constraint_length, blk.block + 2 * blk.depth
+            row["lds_bytes_per_wave"] = (steps + 63) // 64 * 64 * 8 * max(1, (1 << (K - 1)) // 64)
         line = json.dumps(row)
         print(line)
         if args.out:
