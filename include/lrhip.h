@@ -360,6 +360,32 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      lrhip_stage_seek(n0) takes any n0, continues at bit D floor((floor(n0 / n) - L) / D) and counts the
  *                                                      inputs in front of n0 as erasures.  Both stages check their domain before the device is
  *                                                      looked at and fuse with nothing.
+ *   "rsenc:n=N:k=K:gfpoly=P:fcr=F:prim=R:interleave=I" (no block of the reference) Byte -> Byte, a systematic Reed-Solomon encoder over GF(2^8) in the
+ *                                                      polynomial basis.  All keys are required and DECIMAL: gfpoly=285 is 0x11d.  gfpoly is one of
+ *                                                      the 16 primitive polynomials of degree 8 (alpha = 2 must have order 255), fcr = 0 .. 254,
+ *                                                      prim = 1 .. 254 coprime to 255: g(x) = prod_{i < N - K} (x - alpha^((fcr + i) prim)).
+ *                                                      3 <= N <= 255, K >= 1, N - K even and 2 .. 64; N < 255 is the shortened code (255 - N virtual
+ *                                                      zeros at the highest degrees).  Byte j of a codeword is the coefficient of x^(N - 1 - j): the K
+ *                                                      message bytes, then N - K parity bytes.  I = 1 .. 8 codewords are symbol-interleaved: a frame
+ *                                                      is I K bytes in and I N bytes out, byte j of a frame belongs to codeword j mod I at index
+ *                                                      j div I, the output frame is the I K message bytes as they came, then the parity bytes
+ *                                                      interleaved the same way.
+ *   "rsdec:n=N:...:interleave=I:status=0|1"            (no block of the reference) its bounded-distance decoder, the same keys and status.  A frame is
+ *                                                      I N bytes in and the I K corrected message bytes out, followed with status=1 by I status bytes,
+ *                                                      one per codeword: the symbols corrected, 0 .. t = (N - K) / 2 (parity bytes count), or 255 for
+ *                                                      an uncorrectable word, whose message bytes leave as received (Berlekamp-Massey register longer
+ *                                                      than t, not exactly that many locator roots among the N real positions, or a zero error
+ *                                                      magnitude).  No erasure input.
+ *   "packbits:order=msb|lsb"                           (no block of the reference) Bit -> Byte, eight bits (bit 0 of each input byte) per byte on
+ *                                                      absolute bit indices, frames of 8 in and 1 out; msb: the first bit is the most significant.
+ *   "unpackbits:order=msb|lsb"                         (no block of the reference) Byte -> Bit, frames of 1 in and 8 out.
+ *                                                      These four are stages of whole frames, FI bytes in and FO bytes out: frame f is the input bytes
+ *                                                      [f FI, (f + 1) FI) of the stream, a call returns the frames its input completes, possibly none,
+ *                                                      from the lengths alone, and there is no flush.  Any chunking gives the same bytes;
+ *                                                      max_output(N) = FO ceil(N / FI), rate() = FI : FO in lowest terms, memory() = FI - 1;
+ *                                                      lrhip_stage_seek(n0) takes any n0 whose output position is below 2^64, continues at output
+ *                                                      FO floor(n0 / FI) and counts the bytes of that frame in front of n0 as zeros.  They check
+ *                                                      their domain before the device is looked at and fuse with nothing.
  * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
  * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time

@@ -21,7 +21,8 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      SCMFramerBlock, SCMPlusFramerBlock, IDMFramerBlock, AX25FramerBlock, POCSAGFramerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock, InterleaveBlock, DeinterleaveBlock,
                      ArbitraryResamplerBlock, PulseAmplitudeDemodulatorBlock, QuadratureAmplitudeDemodulatorBlock,
-                     ConvolutionalEncoderBlock, ViterbiDecoderBlock)
+                     ConvolutionalEncoderBlock, ViterbiDecoderBlock, ReedSolomonEncoderBlock, ReedSolomonDecoderBlock,
+                     PackBitsBlock, UnpackBitsBlock)
 from .sources import (IQFileSource, RealFileSource, IQFileSink, RealFileSink, WAVFileSink, WAVFileSource, wav_header, parse_wav_header,  # noqa: F401
                       SignalSource, UniformRandomSource)
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401

@@ -1464,6 +1464,147 @@ class ViterbiDecoderBlock(Block):
         return self._execute(x, np.uint8)
 
 
+# ---- Reed-Solomon codes over GF(2^8) and the Bit <-> Byte stages around them (luaradio_amd/csrc/stage_reedsolomon.h)
+def _gcd(a, b):
+    while b:
+        a, b = b, a % b
+    return a
+
+
+def is_primitive_polynomial(gfpoly):
+    """degree 8 over GF(2), and alpha = 2 has order 255 modulo it (16 polynomials, 0x11d the first)"""
+    if not (_is_integer(gfpoly) and 0x100 <= gfpoly <= 0x1ff):
+        return False
+    x, seen = 1, set()
+    for _ in range(255):
+        if x == 0 or x in seen:
+            return False
+        seen.add(x)
+        x <<= 1
+        if x & 0x100:
+            x ^= int(gfpoly)
+    return x == 1
+
+
+def check_reed_solomon_code(who, n, k, options):
+    """the checks both blocks share; the library makes them again on the op string.  Returns (n, k, gfpoly, fcr, prim, interleave)"""
+    unknown = sorted(set(options) - {"gfpoly", "fcr", "prim", "interleave", "status"})
+    if unknown or ("status" in options and who != "rsdec"):
+        raise ValueError("%s: unknown option %r" % (who, unknown[0] if unknown else "status"))
+    if not (_is_integer(n) and 3 <= n <= 255):
+        raise ValueError("%s: n must be 3 .. 255 (got %r)" % (who, n))
+    if not (_is_integer(k) and 1 <= k < n and (n - k) % 2 == 0 and 2 <= n - k <= 64):
+        raise ValueError("%s: k must be 1 .. n - 2 with n - k even and 2 .. 64 (got n = %r, k = %r)" % (who, n, k))
+    gfpoly, fcr, prim, interleave = (options.get("gfpoly", 0x11d), options.get("fcr", 0), options.get("prim", 1), options.get("interleave", 1))
+    if not is_primitive_polynomial(gfpoly):
+        raise ValueError("%s: gfpoly %s is not a primitive polynomial of degree 8" % (who, hex(gfpoly) if _is_integer(gfpoly) else repr(gfpoly)))
+    if not (_is_integer(fcr) and 0 <= fcr <= 254):
+        raise ValueError("%s: fcr must be 0 .. 254 (got %r)" % (who, fcr))
+    if not (_is_integer(prim) and 1 <= prim <= 254 and _gcd(int(prim), 255) == 1):
+        raise ValueError("%s: prim must be 1 .. 254 and coprime to 255 (got %r)" % (who, prim))
+    if not (_is_integer(interleave) and 1 <= interleave <= 8):
+        raise ValueError("%s: interleave must be 1 .. 8 (got %r)" % (who, interleave))
+    return int(n), int(k), int(gfpoly), int(fcr), int(prim), int(interleave)
+
+
+class _FramedBlock(Block):
+    """a stage of whole frames: frame_in input bytes give frame_out output bytes.  Everything is a function of the absolute input index - any
+    chunking, reset, seek or time partition gives the same bytes -, a call returns the frames its input completes, possibly none, and there is no
+    flush.  seek(n0) lands on frame n0 // frame_in and counts the bytes of that frame in front of n0 as zeros."""
+    frame_in = frame_out = 1
+
+    def get_rate(self):
+        return Block.get_rate(self) * self.frame_out / self.frame_in
+
+    def memory(self):
+        """inputs after which a stage started by seek() emits what the uninterrupted stream would"""
+        return self.frame_in - 1
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self.op().split(":")[0])
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
+class ReedSolomonEncoderBlock(_FramedBlock):
+    """ReedSolomonEncoderBlock(n, k[, options]): Byte -> Byte, a systematic Reed-Solomon code over GF(2^8) in the conventional (polynomial) basis.
+    Not a block of the reference.
+    options = {"gfpoly": 0x11d - the field polynomial, one of the 16 primitive polynomials of degree 8; alpha = 2 is a root of it;
+               "fcr": 0 - the first consecutive root, 0 .. 254;
+               "prim": 1 - the root spacing, 1 .. 254 and coprime to 255: g(x) = prod_{i < n - k} (x - alpha^((fcr + i) prim));
+               "interleave": 1 - I = 1 .. 8 codewords per frame, symbol-interleaved as in CCSDS}
+    n <= 255, k >= 1, n - k even and 2 .. 64 (t = (n - k) / 2 = 1 .. 32); n < 255 is the shortened code, its 255 - n virtual bytes zeros at the
+    highest degrees.  Byte j of a codeword is the coefficient of x^(n - 1 - j): the k message bytes first, unchanged, then n - k parity bytes.  A
+    frame is I k bytes in and I n bytes out; byte j of a frame belongs to codeword j mod I at index j div I; the output frame is the I k message
+    bytes as they came, then the I (n - k) parity bytes interleaved the same way.
+    DVB-S: ReedSolomonEncoderBlock(204, 188) (gfpoly 0x11d, fcr 0, prim 1).  CCSDS: ReedSolomonEncoderBlock(255, 223, {"gfpoly": 0x187,
+    "fcr": 112, "prim": 11, "interleave": 1 .. 5}) - in the conventional basis: the dual-basis symbol representation of CCSDS is not applied."""
+    name = "ReedSolomonEncoderBlock"
+    _who = "rsenc"
+
+    def instantiate(self, n, k, options=None):
+        assert n is not None, "Missing argument #1 (n)"
+        assert k is not None, "Missing argument #2 (k)"
+        options = options or {}
+        self.n, self.k, self.gfpoly, self.fcr, self.prim, self.interleave = check_reed_solomon_code(self._who, n, k, options)
+        self.t = (self.n - self.k) // 2
+        self._frames(options)
+        self.add_type_signature([Input("in", types.Byte)], [Output("out", types.Byte)])
+
+    def _frames(self, options):
+        self.frame_in, self.frame_out = self.interleave * self.k, self.interleave * self.n
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; gfpoly is decimal text"""
+        return "%s:n=%d:k=%d:gfpoly=%d:fcr=%d:prim=%d:interleave=%d" % (self._who, self.n, self.k, self.gfpoly, self.fcr, self.prim, self.interleave)
+
+
+class ReedSolomonDecoderBlock(ReedSolomonEncoderBlock):
+    """ReedSolomonDecoderBlock(n, k[, options]): Byte -> Byte, the decoder of ReedSolomonEncoderBlock, with its options and
+              "status": False - True: the I k message bytes of a frame are followed by I status bytes, one per codeword.
+    A frame is I n bytes in and I k corrected message bytes out, in the interleaved order they arrived in.  Bounded-distance decoding: a codeword
+    within Hamming distance t of the received word is found and returned, and its status is the number of symbols corrected, 0 .. t (corrections in
+    parity bytes count).  Otherwise the word is uncorrectable - the locator's register is longer than t, the locator does not have exactly that
+    many roots among the n real positions (a root in the virtual pad of a shortened code is no position), or an error magnitude comes out zero -:
+    its status is 255 and its message bytes leave as received.  There is no erasure input (symbols the demodulator flags as unreliable): out of scope."""
+    name = "ReedSolomonDecoderBlock"
+    _who = "rsdec"
+
+    def _frames(self, options):
+        self.status = bool(options.get("status", False))
+        self.frame_in, self.frame_out = self.interleave * self.n, self.interleave * (self.k + (1 if self.status else 0))
+
+    def op(self):
+        return ReedSolomonEncoderBlock.op(self) + ":status=%d" % self.status
+
+
+class PackBitsBlock(_FramedBlock):
+    """PackBitsBlock([options]): Bit -> Byte, eight bits per byte on absolute bit indices; options = {"order": "msb" - the first bit is the most
+    significant one; "lsb"}.  Bit 0 of each input byte is read; up to 7 bits are carried between calls.  Not a block of the reference."""
+    name = "PackBitsBlock"
+    _who, frame_in, frame_out, _types = "packbits", 8, 1, (types.Bit, types.Byte)
+
+    def instantiate(self, options=None):
+        options = options or {}
+        unknown = sorted(set(options) - {"order"})
+        if unknown:
+            raise ValueError("%s: unknown option %r" % (self._who, unknown[0]))
+        self.order = options.get("order", "msb")
+        if self.order not in ("msb", "lsb"):
+            raise ValueError("%s: unsupported order %r (msb or lsb)" % (self._who, self.order))
+        self.add_type_signature([Input("in", self._types[0])], [Output("out", self._types[1])])
+
+    def op(self):
+        return "%s:order=%s" % (self._who, self.order)
+
+
+class UnpackBitsBlock(PackBitsBlock):
+    """UnpackBitsBlock([options]): Byte -> Bit, eight bits per byte, stateless; options as PackBitsBlock.  Not a block of the reference."""
+    name = "UnpackBitsBlock"
+    _who, frame_in, frame_out, _types = "unpackbits", 1, 8, (types.Byte, types.Bit)
+
+
 # ---- many-ported blocks (luaradio_amd/csrc/stage_interleave.h).  The side of the call with several ports travels as a port table
 # (_lib.port_table), the stages run through lrhip_stage_execute_device alone.
 MAX_CHANNELS = _lib.MAX_PORTS

@@ -6,7 +6,7 @@ tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches pe
 (4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
 PAM / QAM modulators, of the SCM / SCM+ / IDM framers, of the AX.25 / POCSAG framers and of the Varicode decoder instead (modulator_rows,
 ert_framer_rows, packet_framer_rows, varicode_rows); --demodulators prints the rows of the PAM / QAM demodulators (demodulator_rows); --fec those of
-the convolutional encoder and the Viterbi decoder (fec_rows)."""
+the convolutional encoder and the Viterbi decoder (fec_rows); --reed-solomon those of the Reed-Solomon encoder and decoder (reed_solomon_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -28,7 +28,9 @@ def main():
     ap.add_argument("--packet-framers", action="store_true", help="only the AX.25 / POCSAG framer rows (profiles/packet_framer_table.jsonl)")
     ap.add_argument("--varicode", action="store_true", help="only the Varicode decoder rows (profiles/varicode_table.jsonl)")
     ap.add_argument("--fec", action="store_true", help="only the convolutional encoder / Viterbi decoder rows (profiles/fec_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode / --fec: append the rows to this file as well")
+    ap.add_argument("--reed-solomon", action="store_true", help="only the Reed-Solomon encoder / decoder rows (appended to profiles/fec_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode / --fec / --reed-solomon: append the rows to this "
+                                  "file as well")
     args = ap.parse_args()
     if args.modulators:
         return modulator_rows(args)
@@ -42,6 +44,8 @@ def main():
         return varicode_rows(args)
     if args.fec:
         return fec_rows(args)
+    if args.reed_solomon:
+        return reed_solomon_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -314,6 +318,84 @@ def fec_rows(args):
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
+
+
+def reed_solomon_rows(args):
+    """ReedSolomonEncoderBlock and ReedSolomonDecoderBlock (status bytes on) on resident vectors, about 2^24 message bytes per call in whole frames:
+    CCSDS (255, 223) at I = 1 and I = 5 and DVB-S (204, 188); per code the encoder, the decoder on a clean stream, with t errors in one codeword of
+    100, and with t errors in every codeword.  The decoder's input is the device encoder's output, the errors are put in on the host.  Each row
+    stands next to a device-to-device copy that moves the row's input plus output bytes (a buffer of half that size copied once), the two
+    alternating three times.  A record, not an acceptance criterion: the all-errors rows have no outside reference.  --out appends the rows to a
+    file (profiles/fec_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(2)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    def make(cls, n, k, options):
+        blk = cls(n, k, options)
+        blk.rate = 1.0
+        blk.differentiate([types.Byte])
+        blk.initialize()
+        return blk
+
+    ccsds = {"gfpoly": 0x187, "fcr": 112, "prim": 11}
+    for name, n, k, options in (("CCSDS (255,223) I=1", 255, 223, dict(ccsds)), ("CCSDS (255,223) I=5", 255, 223, dict(ccsds, interleave=5)),
+                                ("DVB-S (204,188)", 204, 188, {})):
+        I, t = options.get("interleave", 1), (n - k) // 2
+        frames = -(-(1 << 24) // (I * k))
+        message = torch.from_numpy(rng.integers(0, 256, frames * I * k).astype(np.uint8)).cuda()
+        coded = torch.empty(frames * I * n, dtype=torch.uint8, device="cuda")
+        enc = make(lr.ReedSolomonEncoderBlock, n, k, options)
+        assert enc.process_device(message.data_ptr(), len(message), coded.data_ptr(), len(coded)) == len(coded)
+        torch.cuda.synchronize()
+        words = coded.cpu().numpy().reshape(frames, n, I).transpose(0, 2, 1).reshape(frames * I, n)      # [codeword][byte]
+        inputs = [("encoder", enc, message, len(coded))]
+        for label, share in (("decoder, clean", 0.0), ("decoder, t errors in 1 of 100", 0.01), ("decoder, t errors in every codeword", 1.0)):
+            hit = words.copy()
+            rows = np.arange(len(hit)) if share == 1.0 else np.flatnonzero(rng.random(len(hit)) < share)
+            where = np.argsort(rng.random((len(rows), n)), axis=1)[:, :t]                                # t distinct positions per codeword
+            hit[rows[:, None], where] ^= rng.integers(1, 256, where.shape).astype(np.uint8)
+            x = torch.from_numpy(np.ascontiguousarray(hit.reshape(frames, I, n).transpose(0, 2, 1)).reshape(-1)).cuda()
+            inputs.append((label, make(lr.ReedSolomonDecoderBlock, n, k, dict(options, status=True)), x, frames * I * (k + 1)))
+        for label, blk, x, n_out in inputs:
+            y = torch.empty(n_out + 64, dtype=torch.uint8, device="cuda")
+            half = (len(x) + n_out) // 2
+            src, dst = torch.empty(half, dtype=torch.uint8, device="cuda"), torch.empty(half, dtype=torch.uint8, device="cuda")
+            ms, ms_copy = [], []
+            for _ in range(3):
+                blk.reset()
+                assert blk.process_device(x.data_ptr(), len(x), y.data_ptr(), n_out) == n_out
+                ms.append(timed(lambda: blk.process_device(x.data_ptr(), len(x), y.data_ptr(), n_out)))
+                ms_copy.append(timed(lambda: dst.copy_(src)))
+            row = {"row": "ReedSolomon %s %s" % (name, label), "message_bytes": frames * I * k, "codewords": frames * I, "op": blk.op(), "ms": ms,
+                   "copy_ms": ms_copy, "copy_bytes_moved": 2 * half, "share_of_copy": round(min(ms_copy) / min(ms), 3),
+                   "GB/s_message": round(frames * I * k / min(ms) / 1e6, 2)}
+            if label != "encoder":
+                status = y[:n_out].cpu().numpy().reshape(frames, I * (k + 1))[:, I * k:]
+                row["codewords_corrected"] = int(np.count_nonzero((status > 0) & (status <= t)))
+                row["codewords_uncorrectable"] = int(np.count_nonzero(status == 255))
+            line = json.dumps(row)
+            print(line)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(line + "\n")
 
 
 def ert_framer_rows(args):
