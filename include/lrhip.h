@@ -386,6 +386,26 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      lrhip_stage_seek(n0) takes any n0 whose output position is below 2^64, continues at output
  *                                                      FO floor(n0 / FI) and counts the bytes of that frame in front of n0 as zeros.  They check
  *                                                      their domain before the device is looked at and fuse with nothing.
+ *   "puncture:pattern=B"                               (no block of the reference) Bit -> Bit.  B is 2 .. 64 characters 0 / 1, not all 0: a stage of
+ *                                                      whole frames as the four above, counted in elements, len(B) in and popcount(B) out, element j
+ *                                                      of a frame kept where B[j] is 1.  Bytes are moved, never interpreted.
+ *   "depuncture:pattern=B:input=llr|bit"               (no block of the reference) the inverse framing, Float32 (llr) or Bit (bit) -> Float32:
+ *                                                      popcount(B) elements in, len(B) Float32 out, +0.0f - an erasure to "viterbi" - where B[j] is 0.
+ *                                                      llr: the four bytes of an input are moved as they are (a NaN stays that NaN); bit: bit 0 of the
+ *                                                      byte is read, 0 gives +1.0f and 1 gives -1.0f, which "viterbi" at scale=127 reads as its hard
+ *                                                      input.  Contract of the frame stages, with elements for bytes.
+ *   "convinterleave:branches=I:step=M"                 (no block of the reference) Byte -> Byte, 1 : 1, the convolutional (Forney) interleaver:
+ *                                                      I = 2 .. 256, M = 1 .. 256, depth D = (I - 1) M I <= 65536.  With j = i mod I on the absolute
+ *                                                      index i, out[i] = in[i - j M I] and in[negative] = 0.
+ *   "convdeinterleave:branches=I:step=M"               its inverse up to a delay of D bytes: out[i] = in[i - (I - 1 - j) M I].  Both carry the last D
+ *                                                      input bytes between calls; max_output(n) = n, memory() = D, lrhip_stage_seek(n0) takes any n0
+ *                                                      and continues at output n0 with zeros for everything in front.
+ *   "scrambler:table=HEX:offset=K"                     (no block of the reference) Byte -> Byte, 1 : 1, additive: HEX is 2 P hexadecimal digits, the
+ *                                                      P = 1 .. 8192 bytes of the table, K = 0 .. P - 1; out[i] = in[i] ^ table[(i + K) mod P] on the
+ *                                                      absolute index i (reduced mod P before K is added: no i below 2^64 wraps).  memory() = 0,
+ *                                                      lrhip_stage_seek(n0) takes any n0.  The library knows no polynomial: the caller builds tables.
+ *                                                      All keys of these five are required; they check their domain before the device is looked at
+ *                                                      and fuse with nothing.
  * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
  * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time

@@ -22,7 +22,9 @@ from .blocks import (BandpassFilterBlock, BandstopFilterBlock, DownsamplerBlock,
                      PulseAmplitudeModulatorBlock, QuadratureAmplitudeModulatorBlock, PLLBlock, InterleaveBlock, DeinterleaveBlock,
                      ArbitraryResamplerBlock, PulseAmplitudeDemodulatorBlock, QuadratureAmplitudeDemodulatorBlock,
                      ConvolutionalEncoderBlock, ViterbiDecoderBlock, ReedSolomonEncoderBlock, ReedSolomonDecoderBlock,
-                     PackBitsBlock, UnpackBitsBlock)
+                     PackBitsBlock, UnpackBitsBlock, PunctureBlock, DepunctureBlock, ConvolutionalInterleaverBlock,
+                     ConvolutionalDeinterleaverBlock, AdditiveScramblerBlock, lfsr_sequence, dvb_energy_dispersal_table,
+                     ccsds_randomizer_table)
 from .sources import (IQFileSource, RealFileSource, IQFileSink, RealFileSink, WAVFileSink, WAVFileSource, wav_header, parse_wav_header,  # noqa: F401
                       SignalSource, UniformRandomSource)
 from .meters import BenchmarkSink, RawFileSource, ZeroSource  # noqa: F401
@@ -31,6 +33,7 @@ from .graph import DeviceGraph  # noqa: F401
 from .composites import (Chain, CompositeBlock, DecimatorBlock, InterpolatorBlock, RationalResamplerBlock, TunerBlock, WBFMMonoDemodulator,  # noqa: F401
                          NBFMDemodulator, AMEnvelopeDemodulator, SSBDemodulator, SSBModulator, wbfm_mono_receiver, am_envelope_receiver,
                          ssb_receiver, nbfm_receiver, ax25_receiver, pocsag_receiver, bpsk31_receiver, ert_receiver, am_synchronous_receiver,
-                         wbfm_stereo_receiver, rds_receiver)
+                         wbfm_stereo_receiver, rds_receiver, dvbs_fec_encoder, dvbs_fec_decoder, dvbs_fec_encoder_blocks,
+                         dvbs_fec_decoder_blocks, DVBS_PUNCTURE, DVBS_DEPTH, DVBS_FILL_PACKETS)
 
 version = "0.1.0"

@@ -1605,6 +1605,196 @@ class UnpackBitsBlock(PackBitsBlock):
     _who, frame_in, frame_out, _types = "unpackbits", 1, 8, (types.Byte, types.Bit)
 
 
+# ---- puncturing, the Forney interleaver and the additive scrambler (luaradio_amd/csrc/stage_fecglue.h): what joins the convolutional and the
+# Reed-Solomon stages into a standard concatenated link.  dvbs_fec_encoder / dvbs_fec_decoder in composites.py are the DVB-S chain.
+def check_puncture_pattern(who, pattern):
+    """the checks both blocks share; the library makes them again on the op string"""
+    if not isinstance(pattern, str) or set(pattern) - set("01"):
+        raise ValueError("%s: pattern must be a string of 0 / 1 characters, got %r" % (who, pattern))
+    if not 2 <= len(pattern) <= 64:
+        raise ValueError("%s: pattern must be 2 .. 64 characters (got %d)" % (who, len(pattern)))
+    if "1" not in pattern:
+        raise ValueError("%s: pattern must not be all 0 (got %r)" % (who, pattern))
+    return pattern
+
+
+class PunctureBlock(_FramedBlock):
+    """PunctureBlock(pattern): Bit -> Bit.  pattern is 2 .. 64 characters 0 / 1 with at least one 1; a frame is len(pattern) elements in and
+    pattern.count("1") out, element j of a frame kept where pattern[j] == "1".  Bytes are moved, never interpreted.  Behind
+    ConvolutionalEncoderBlock(7, [0o171, 0o133]) the patterns of composites.DVBS_PUNCTURE give the DVB-S rates.  Not a block of the reference."""
+    name = "PunctureBlock"
+    _who = "puncture"
+
+    def instantiate(self, pattern):
+        assert pattern is not None, "Missing argument #1 (pattern)"
+        self.pattern = check_puncture_pattern(self._who, pattern)
+        self.frame_in, self.frame_out = len(pattern), pattern.count("1")
+        self.add_type_signature([Input("in", types.Bit)], [Output("out", types.Bit)])
+
+    def op(self):
+        return "puncture:pattern=%s" % self.pattern
+
+
+class DepunctureBlock(_FramedBlock):
+    """DepunctureBlock(pattern[, options]): Float32 -> Float32, or Bit -> Float32 with options = {"soft": False}; the inverse framing of
+    PunctureBlock: pattern.count("1") elements in, len(pattern) Float32 out, +0.0 where pattern[j] == "0" - the LLR ViterbiDecoderBlock counts as an
+    erasure.  soft (the default): the LLRs are moved as their 32 bits, a NaN stays that NaN.  Bit: bit 0 of the input byte is read, 0 gives +1.0 and
+    1 gives -1.0, the demodulators' sign convention, so that ViterbiDecoderBlock(..., {"scale": 127}) behind it sees exactly its hard input.
+    Not a block of the reference."""
+    name = "DepunctureBlock"
+    _who = "depuncture"
+
+    def instantiate(self, pattern, options=None):
+        assert pattern is not None, "Missing argument #1 (pattern)"
+        options = options or {}
+        unknown = sorted(set(options) - {"soft"})
+        if unknown:
+            raise ValueError("depuncture: unknown option %r" % (unknown[0],))
+        self.pattern = check_puncture_pattern(self._who, pattern)
+        self.soft = bool(options.get("soft", True))
+        self.frame_in, self.frame_out = pattern.count("1"), len(pattern)
+        self.add_type_signature([Input("in", types.Float32 if self.soft else types.Bit)], [Output("out", types.Float32)])
+
+    def op(self):
+        return "depuncture:pattern=%s:input=%s" % (self.pattern, "llr" if self.soft else "bit")
+
+    def process(self, x):
+        return self._execute(x, np.float32)
+
+
+class ConvolutionalInterleaverBlock(Block):
+    """ConvolutionalInterleaverBlock(branches, step): Byte -> Byte, the convolutional (Forney) interleaver with I = branches = 2 .. 256 and
+    M = step = 1 .. 256, depth D = (I - 1) M I <= 65536: with j = i mod I on the absolute byte index i, out[i] = in[i - j M I], in[negative] = 0 (the
+    zero-filled FIFOs of the standards).  ConvolutionalDeinterleaverBlock undoes it up to a delay of D bytes.  DVB-S: (12, 17), D = 2244 bytes = 11
+    packets of 204; the sync bytes, at multiples of 204, ride branch 0 and are not delayed.  The last D input bytes are carried between calls;
+    seek(n0) continues at output n0 with zeros for everything in front.  Not a block of the reference."""
+    name = "ConvolutionalInterleaverBlock"
+    _who = "convinterleave"
+
+    def instantiate(self, branches, step):
+        assert branches is not None, "Missing argument #1 (branches)"
+        assert step is not None, "Missing argument #2 (step)"
+        if not (_is_integer(branches) and 2 <= branches <= 256):
+            raise ValueError("%s: branches must be 2 .. 256 (got %r)" % (self._who, branches))
+        if not (_is_integer(step) and 1 <= step <= 256):
+            raise ValueError("%s: step must be 1 .. 256 (got %r)" % (self._who, step))
+        self.branches, self.step = int(branches), int(step)
+        self.depth = (self.branches - 1) * self.step * self.branches
+        if self.depth > 65536:
+            raise ValueError("%s: the depth (branches - 1) * step * branches = %d must be at most 65536" % (self._who, self.depth))
+        self.add_type_signature([Input("in", types.Byte)], [Output("out", types.Byte)])
+
+    def memory(self):
+        """inputs after which a stage started by seek() emits what the uninterrupted stream would"""
+        return self.depth
+
+    def op(self):
+        return "%s:branches=%d:step=%d" % (self._who, self.branches, self.step)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip %s object" % self._who)
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
+class ConvolutionalDeinterleaverBlock(ConvolutionalInterleaverBlock):
+    """ConvolutionalDeinterleaverBlock(branches, step): Byte -> Byte, out[i] = in[i - (I - 1 - j) M I] with j = i mod I; behind
+    ConvolutionalInterleaverBlock(branches, step) the stream comes back delayed by D = (I - 1) M I bytes, the first D outputs zeros.  Both streams
+    count from the same byte 0: there is no search for the branch phase.  Not a block of the reference."""
+    name = "ConvolutionalDeinterleaverBlock"
+    _who = "convdeinterleave"
+
+
+def lfsr_sequence(taps, seed_bits, nbits):
+    """nbits bits (a multiple of 8) of the linear recurrence s[m] = xor of s[m - i] for i in taps, from seed_bits[i - 1] = s[-i], packed MSB first
+    into a uint8 array: the stuff of AdditiveScramblerBlock tables"""
+    taps = [int(t) for t in taps]
+    order = max(taps)
+    if min(taps) < 1 or len(seed_bits) != order:
+        raise ValueError("lfsr_sequence: taps are positive and the seed has max(taps) = %d bits (got %d)" % (order, len(seed_bits)))
+    if nbits < 8 or nbits % 8:
+        raise ValueError("lfsr_sequence: nbits must be a positive multiple of 8 (got %r)" % (nbits,))
+    s = np.zeros(order + nbits, np.uint8)
+    s[:order] = [int(b) & 1 for b in reversed(list(seed_bits))]
+    for m in range(order, order + nbits):
+        v = 0
+        for t in taps:
+            v ^= s[m - t]
+        s[m] = v
+    return np.packbits(s[order:])
+
+
+def dvb_energy_dispersal_table(frame=188):
+    """the energy dispersal of EN 300 421 as a table for AdditiveScramblerBlock, one period of 8 transport packets: byte 0 is 0xFF (the sync
+    inversion 0x47 -> 0xB8); the PRBS 1 + x^14 + x^15, seed 100101010000000, runs from byte 1; at the seven other sync bytes, 188 q, the entry is 0
+    but the PRBS advances.  frame=189: every frame has a 189th entry that is 0 and does not advance the PRBS, for a stream of
+    ReedSolomonDecoderBlock(204, 188, {"status": True})"""
+    if frame not in (188, 189):
+        raise ValueError("dvb_energy_dispersal_table: frame must be 188 or 189 (got %r)" % (frame,))
+    prbs = lfsr_sequence((14, 15), [1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0], 8 * 1503)
+    packets = np.concatenate([[0xFF], prbs]).astype(np.uint8).reshape(8, 188)
+    packets[1:, 0] = 0
+    table = np.zeros((8, frame), np.uint8)
+    table[:, :188] = packets
+    return table.ravel()
+
+
+def ccsds_randomizer_table(nbytes):
+    """nbytes of the CCSDS pseudo-randomizer h(x) = x^8 + x^7 + x^5 + x^3 + 1 from the all-ones state (ff 48 0e c0 9a ...; its period is 255 bits).
+    A table as long as the transfer frame restarts it at every frame"""
+    if not (_is_integer(nbytes) and 1 <= nbytes <= 8192):
+        raise ValueError("ccsds_randomizer_table: nbytes must be 1 .. 8192 (got %r)" % (nbytes,))
+    taps = (1, 3, 5, 8)
+    # the seed whose first eight outputs are ones: the recurrence run backwards from them, s[m - 8] = s[m] ^ s[m - 1] ^ s[m - 3] ^ s[m - 5]
+    s = [1] * 8                                                   # s[0 .. 7]; s[-1], s[-2], ... are put in front
+    for _ in range(8):
+        s.insert(0, s[7] ^ s[6] ^ s[4] ^ s[2])
+    return lfsr_sequence(taps, s[7::-1], 8 * int(nbytes))
+
+
+class AdditiveScramblerBlock(Block):
+    """AdditiveScramblerBlock(table[, options]): Byte -> Byte, out[i] = in[i] ^ table[(i + offset) mod P] on the absolute byte index i; the same
+    block descrambles.  table is 1 .. 8192 bytes (anything np.asarray turns into integers 0 .. 255), options = {"offset": 0 - 0 .. P - 1}.  The
+    device knows no polynomial: lfsr_sequence, dvb_energy_dispersal_table and ccsds_randomizer_table build tables.  Not a block of the reference."""
+    name = "AdditiveScramblerBlock"
+
+    def instantiate(self, table, options=None):
+        assert table is not None, "Missing argument #1 (table)"
+        options = options or {}
+        unknown = sorted(set(options) - {"offset"})
+        if unknown:
+            raise ValueError("scrambler: unknown option %r" % (unknown[0],))
+        try:
+            values = np.asarray(table)
+            ok = values.ndim == 1 and values.dtype.kind in "ui" and values.size > 0 and int(values.min()) >= 0 and int(values.max()) <= 255
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("scrambler: the table must be a vector of integers 0 .. 255")
+        if not 1 <= values.size <= 8192:
+            raise ValueError("scrambler: the table has %d bytes, it must be 1 .. 8192" % values.size)
+        self.table = values.astype(np.uint8)
+        self.offset = options.get("offset", 0)
+        if not (_is_integer(self.offset) and 0 <= self.offset < len(self.table)):
+            raise ValueError("scrambler: offset must be 0 .. %d, the table's length less one (got %r)" % (len(self.table) - 1, self.offset))
+        self.offset = int(self.offset)
+        self.add_type_signature([Input("in", types.Byte)], [Output("out", types.Byte)])
+
+    def memory(self):
+        return 0
+
+    def op(self):
+        """the stage as lrhip_unary_create takes it; the table is hexadecimal text, two digits per byte"""
+        return "scrambler:table=%s:offset=%d" % (self.table.tobytes().hex(), self.offset)
+
+    def initialize(self):
+        self._set_stage(_lib.load().lrhip_unary_create(self.op().encode(), 0.0, 0.0, 0, 0), "Creating lrhip scrambler object")
+
+    def process(self, x):
+        return self._execute(x, np.uint8)
+
+
 # ---- many-ported blocks (luaradio_amd/csrc/stage_interleave.h).  The side of the call with several ports travels as a port table
 # (_lib.port_table), the stages run through lrhip_stage_execute_device alone.
 MAX_CHANNELS = _lib.MAX_PORTS

@@ -42,6 +42,7 @@
 #include "kernels_arbresample.h"
 #include "kernels_viterbi.h"
 #include "kernels_reedsolomon.h"
+#include "kernels_fecglue.h"
 
 using namespace lrhip;
 
@@ -80,6 +81,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
 #include "stage_arbresample.h"
 #include "stage_viterbi.h"
 #include "stage_reedsolomon.h"
+#include "stage_fecglue.h"
 #include "chain_plan.h"
 
 // =====================================================================================================
@@ -344,6 +346,8 @@ lrhip_stage_t *lrhip_unary_create(const char *op, float re, float im, int consta
         {"wavpack", port_stage_create}, {"wavunpack", port_stage_create}, {"signalsource", source_create}, {"uniformrandomsource", source_create},
         {"arbresampler", arbresampler_create}, {"convenc", convenc_create}, {"viterbi", viterbi_create},
         {"rsenc", reedsolomon_create}, {"rsdec", reedsolomon_create}, {"packbits", bitpack_create}, {"unpackbits", bitpack_create},
+        {"puncture", puncture_create}, {"depuncture", puncture_create}, {"convinterleave", convinterleave_create},
+        {"convdeinterleave", convinterleave_create}, {"scrambler", scrambler_create},
         {"rdsframer", plain_create<RfStage, 8>}, {"scmframer", plain_create<EfStage<EF_SCM>, EfProto<EF_SCM>::REC>},
         {"scmplusframer", plain_create<EfStage<EF_SCMPLUS>, EfProto<EF_SCMPLUS>::REC>}, {"idmframer", plain_create<EfStage<EF_IDM>, EfProto<EF_IDM>::REC>},
         {"ax25framer", plain_create<AxStage, AX_REC>}, {"pocsagframer", plain_create<PgStage, PG_REC>}, {"varicodedecoder", plain_create<VcStage, 1>}};

@@ -118,6 +118,20 @@ struct OpFields {
         out = v;
         return true;
     }
+    // an even number of hexadecimal digits, at least two: the bytes they spell, the first pair first
+    bool hex(const char *key, std::vector<uint8_t> &out) const
+    {
+        if (missing(key)) return false;
+        const std::string &v = text(key);
+        if (v.empty() || v.size() % 2 || v.find_first_not_of("0123456789abcdefABCDEF") != std::string::npos) {
+            set_error("%s: %s must be an even number of hexadecimal digits, at least two", who.c_str(), key);
+            return false;
+        }
+        auto digit = [](char ch) { return ch <= '9' ? ch - '0' : (ch | 0x20) - 'a' + 10; };
+        out.resize(v.size() / 2);
+        for (size_t i = 0; i < out.size(); i++) out[i] = (uint8_t)(digit(v[2 * i]) << 4 | digit(v[2 * i + 1]));
+        return true;
+    }
     // a comma list of Float32 values, possibly empty: each strtod text (decimal or hexadecimal floating point) rounded to Float32, so %.9g and %a
     // give back the Float32 they were printed from.  No trailing comma; entry / hint / ends word the messages ("bad <entry> N<hint>", "<ends> with a
     // comma").  cap > 0: reading stops once more than cap values are out, for a caller that refuses the list by its count anyway.

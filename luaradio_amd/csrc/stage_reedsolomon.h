@@ -4,9 +4,10 @@
 // (part of liblrhip.so; included by lrhip.hip after stage_viterbi.h, one translation unit)
 #pragma once
 
-// A stage of whole frames: FI input bytes give FO output bytes (rs_plan.h).  Carried: the bytes behind the last complete frame (two buffers,
-// ping-pong, written by frame_carry_kernel) and the absolute count Q of inputs consumed.  A call returns the frames that its inputs complete - from
-// the lengths alone, nothing is read back - and may return 0.  There is no flush
+// A stage of whole frames: FI input elements give FO output elements (rs_plan.h), an element being in_size bytes in and out_size bytes out - one
+// byte each for the stages of this file, four where stage_fecglue.h moves Float32.  Carried: the elements behind the last complete frame (two
+// buffers, ping-pong, written by frame_carry_kernel as bytes) and the absolute count Q of inputs consumed.  A call returns the frames that its
+// inputs complete - from the lengths alone, nothing is read back - and may return 0.  There is no flush
 struct FramedStage : lrhip_stage {
     rsplan::Frame frame{1, 1};
     const char *who = "";
@@ -27,7 +28,7 @@ struct FramedStage : lrhip_stage {
     int seek_to(uint64_t n0)
     {
         cur = 0; Q = n0;
-        return (zero_fill(carry[0], frame.fi) || zero_fill(carry[1], frame.fi)) ? -1 : 0;
+        return (zero_fill(carry[0], (size_t)frame.fi * in_size) || zero_fill(carry[1], (size_t)frame.fi * in_size)) ? -1 : 0;
     }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
     {
@@ -37,7 +38,7 @@ struct FramedStage : lrhip_stage {
         *n0_out = pos;
         return 0;
     }
-    // frames 0 .. nf - 1 of [carry | in], c bytes of it carried
+    // frames 0 .. nf - 1 of [carry | in], c elements of it carried
     virtual int launch(const uint8_t *carried, const uint8_t *in_dev, uint8_t *out_dev, uint32_t c, long nf) = 0;
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
@@ -54,8 +55,9 @@ struct FramedStage : lrhip_stage {
         if (nf && launch(carried, (const uint8_t *)in_dev, (uint8_t *)out_dev, c, (long)nf)) return -1;
         const unsigned count = rsplan::carried(Q + n, frame);
         if (count) {
-            hipLaunchKernelGGL(frame_carry_kernel, dim3(grid_for(count, 256)), dim3(256), 0, ctx().stream, carried, (const uint8_t *)in_dev,
-                               (uint8_t *)carry[cur ^ 1].p, c, nf * frame.fi, count);
+            const unsigned es = (unsigned)in_size;
+            hipLaunchKernelGGL(frame_carry_kernel, dim3(grid_for(count * es, 256)), dim3(256), 0, ctx().stream, carried, (const uint8_t *)in_dev,
+                               (uint8_t *)carry[cur ^ 1].p, c * es, nf * frame.fi * es, count * es);
             LR_LAUNCH_CHECK();
         }
         cur ^= 1;

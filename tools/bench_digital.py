@@ -6,7 +6,8 @@ tools/bench_blocks.py.  Prints one JSON object per row: ms per call, launches pe
 (4 B/sample read; + 4 B/sample written for the clock recovery).  --modulators, --ert-framers and --packet-framers print the rows of the
 PAM / QAM modulators, of the SCM / SCM+ / IDM framers, of the AX.25 / POCSAG framers and of the Varicode decoder instead (modulator_rows,
 ert_framer_rows, packet_framer_rows, varicode_rows); --demodulators prints the rows of the PAM / QAM demodulators (demodulator_rows); --fec those of
-the convolutional encoder and the Viterbi decoder (fec_rows); --reed-solomon those of the Reed-Solomon encoder and decoder (reed_solomon_rows)."""
+the convolutional encoder and the Viterbi decoder (fec_rows); --reed-solomon those of the Reed-Solomon encoder and decoder (reed_solomon_rows);
+--fecglue those of the puncturing, interleaving and scrambling stages and of the two DVB-S FEC chains (fecglue_rows)."""
 import argparse
 import ctypes as C
 import json
@@ -29,7 +30,9 @@ def main():
     ap.add_argument("--varicode", action="store_true", help="only the Varicode decoder rows (profiles/varicode_table.jsonl)")
     ap.add_argument("--fec", action="store_true", help="only the convolutional encoder / Viterbi decoder rows (profiles/fec_table.jsonl)")
     ap.add_argument("--reed-solomon", action="store_true", help="only the Reed-Solomon encoder / decoder rows (appended to profiles/fec_table.jsonl)")
-    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode / --fec / --reed-solomon: append the rows to this "
+    ap.add_argument("--fecglue", action="store_true", help="only the puncture / depuncture / interleaver / scrambler / DVB-S chain rows (appended to "
+                                                           "profiles/fec_table.jsonl)")
+    ap.add_argument("--out", help="with --modulators / --demodulators / --ert-framers / --packet-framers / --varicode / --fec / --reed-solomon / --fecglue: append the rows to this "
                                   "file as well")
     args = ap.parse_args()
     if args.modulators:
@@ -46,6 +49,8 @@ def main():
         return fec_rows(args)
     if args.reed_solomon:
         return reed_solomon_rows(args)
+    if args.fecglue:
+        return fecglue_rows(args)
     import numpy as np
     import torch
     import luaradio_amd as lr
@@ -396,6 +401,80 @@ def reed_solomon_rows(args):
             if args.out:
                 with open(args.out, "a") as f:
                     f.write(line + "\n")
+
+
+def fecglue_rows(args):
+    """PunctureBlock and DepunctureBlock at rate 3/4, the (12, 17) and (52, 4) interleavers, the 1504-byte scrambler and the DVB-S chains
+    dvbs_fec_encoder / dvbs_fec_decoder at 3/4 end to end, on resident vectors of about 2^24 input bytes per call, successive calls continuing one
+    stream.  Each row stands next to a device-to-device copy that moves the row's input plus output bytes (a buffer of half that size copied
+    once), the two alternating three times.  The four stages are pure data movement, so share_of_copy is their figure; the chains are a record.
+    --out appends the rows to a file (profiles/fec_table.jsonl)."""
+    import numpy as np
+    import torch
+    import luaradio_amd as lr
+    from luaradio_amd import types
+
+    lr.init(0)
+    lr.adopt_torch_stream()
+    rng = np.random.default_rng(3)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / args.reps, 4)
+
+    def made(blk, in_type):
+        blk.rate = 1.0
+        blk.differentiate([in_type])
+        blk.initialize()
+        return blk
+
+    pattern = lr.DVBS_PUNCTURE["3/4"]
+    n = 1 << 24
+    packets = n // 188
+    ts = rng.integers(0, 256, (packets, 188)).astype(np.uint8)
+    ts[:, 0] = 0x47
+    rows = [("Puncture 3/4", made(lr.PunctureBlock(pattern), types.Bit), rng.integers(0, 2, n // 6 * 6).astype(np.uint8)),
+            ("Depuncture 3/4 (Float32 LLRs)", made(lr.DepunctureBlock(pattern), types.Float32), rng.standard_normal(n // 16 * 4).astype(np.float32)),
+            ("ConvolutionalInterleaver (12,17)", made(lr.ConvolutionalInterleaverBlock(12, 17), types.Byte), rng.integers(0, 256, n).astype(np.uint8)),
+            ("ConvolutionalDeinterleaver (12,17)", made(lr.ConvolutionalDeinterleaverBlock(12, 17), types.Byte), rng.integers(0, 256, n).astype(np.uint8)),
+            ("ConvolutionalInterleaver (52,4)", made(lr.ConvolutionalInterleaverBlock(52, 4), types.Byte), rng.integers(0, 256, n).astype(np.uint8)),
+            ("AdditiveScrambler DVB 1504-byte table", made(lr.AdditiveScramblerBlock(lr.dvb_energy_dispersal_table()), types.Byte),
+             rng.integers(0, 256, n).astype(np.uint8)),
+            ("dvbs_fec_encoder 3/4", lr.dvbs_fec_encoder("3/4"), ts.ravel()),
+            ("dvbs_fec_decoder 3/4 (Float32 LLRs)", lr.dvbs_fec_decoder("3/4"), (4.0 * rng.standard_normal(n // 16 * 4)).astype(np.float32))]
+    for label, obj, host in rows:
+        x = torch.from_numpy(host).cuda()
+        cap = obj.max_output(len(x))
+        out_size = obj.out_type.dtype.itemsize if isinstance(obj, lr.Chain) else obj.get_output_type().dtype.itemsize
+        y = torch.empty(cap * out_size + 64, dtype=torch.uint8, device="cuda")
+        in_bytes = len(x) * host.dtype.itemsize
+        ms, ms_copy, counts = [], [], []
+        for _ in range(3):
+            obj.reset()
+            counts = [obj.process_device(x.data_ptr(), len(x), y.data_ptr(), cap) for _ in range(2)]      # the second call is the steady state
+            half = (in_bytes + counts[1] * out_size) // 2
+            src, dst = torch.empty(half, dtype=torch.uint8, device="cuda"), torch.empty(half, dtype=torch.uint8, device="cuda")
+            ms.append(timed(lambda: obj.process_device(x.data_ptr(), len(x), y.data_ptr(), cap)))
+            ms_copy.append(timed(lambda: dst.copy_(src)))
+        row = {"row": "FEC glue %s" % label, "input_bytes": in_bytes, "output_bytes": counts[1] * out_size, "ms": ms, "copy_ms": ms_copy,
+               "copy_bytes_moved": 2 * half, "share_of_copy": round(min(ms_copy) / min(ms), 3), "GB/s_input": round(in_bytes / min(ms) / 1e6, 2)}
+        if isinstance(obj, lr.Chain):
+            row["launches"] = obj.last_launches
+        else:
+            row["op"] = obj.op()[:80]
+        line = json.dumps(row)
+        print(line)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(line + "\n")
 
 
 def ert_framer_rows(args):
