@@ -406,6 +406,22 @@ lrhip_stage_t *lrhip_powersquelch_create(double alpha, double threshold, int inp
  *                                                      lrhip_stage_seek(n0) takes any n0.  The library knows no polynomial: the caller builds tables.
  *                                                      All keys of these five are required; they check their domain before the device is looked at
  *                                                      and fuse with nothing.
+ *   "pll:alpha=A:beta=B:fmin=F0:fmax=F1:mult=M:port=out|error"
+ *                                                      PLLBlock, ComplexFloat32 -> ComplexFloat32 cis(phi_multiplied) (port=out, the default) or
+ *                                                      Float32 phase error (port=error).  A, B, F0, F1 (radians per sample) are required and finite,
+ *                                                      M defaults to 1.  While the loop is in lock a call is computed in parallel segments whose
+ *                                                      speculated entry states are verified against their predecessors' exits, and rejected segments
+ *                                                      are rerun serially (csrc/pll_plan.h).  The result is the reference's serial recurrence with
+ *                                                      perturbations at accepted segment boundaries of at most 2^-22 rad in phi_locked (modulo 2 pi)
+ *                                                      and 2^-22 B / A in freq_locked.  These tolerances bound phi_locked and freq_locked, and with
+ *                                                      them the error port; they do NOT bound phi_multiplied, which is never fed back: each accepted
+ *                                                      boundary can move it by up to (|M| + |M - 1|) 2^-22 rad, so the out port's distance from the
+ *                                                      serial loop grows with the stream length and the multiplier (measured on the host at M = 20,
+ *                                                      carrier + 0.1 noise, segments of 64: 4e-7 after 2^15 samples, 8e-7 after 2^16 and rising; at
+ *                                                      M = 3 it stays at Float32 rounding).  Segments whose mean |error| is under 1e-5 rad (a tone
+ *                                                      without noise) or over pi / 4 (no lock) are always rerun serially.  The test knob
+ *                                                      "speculate=0" runs the serial recurrence throughout and gives its value at any length.
+ *                                                      memory() = -1: no time partitions.  The stage fuses with nothing.
  * A source runs with in = NULL and n_in = the number of samples to generate, in every execute / submit entry point; a chain takes one as its
  * first stage only.
  * The sampler, the clocksampler, the preamblesampler, the manchesterdecoder, the varicodedecoder, the rdsframer, the three ERT framers, the ax25framer and the pocsagframer have memory() -1: chains holding them refuse time

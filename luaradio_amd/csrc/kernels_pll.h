@@ -5,7 +5,7 @@
 // call of n samples, segments of C:
 //   speculate  one lane per segment: warm-up over [kC - W, kC) without output (lanes with kC <= W start at sample 0 from the carried state, which
 //              is exact), then the segment: entry e_k, exit x_k, and the segment's phi_multiplied increment modulo 2 pi
-//   verify     segment k is accepted when e_k agrees with x_(k-1) within tol and the mean |err| over it is under pi / 4 (in lock); the number of rejections is the call's one 8-byte read-back
+//   verify     segment k is accepted when e_k agrees with x_(k-1) within tol and the mean |err| over it is under pi / 4 (in lock) and over PLL_LOCK_FLOOR (the input carries dither); the number of rejections is the call's one 8-byte read-back
 //   repair     only when something was rejected: one thread walks the rejected segments in stream order from their predecessors' true exits
 //              (out of lock: the serial recurrence at single-lane speed, which is what the reference runs)
 //   prefix     phi_multiplied is never fed back: an exclusive scan of the segments' totals modulo 2 pi gives every segment's entry value

@@ -7,6 +7,16 @@
 // none at sample 0 of a call (the carried state is exact).  phi_multiplied is never fed back; it is the prefix sum of freq * mult + alpha * err
 // over that trajectory, carried modulo 2 pi.
 //
+// The boundary tolerances bound phi_locked and freq_locked, NOT phi_multiplied.  A perturbation (d, g) of (phi_locked, freq_locked) at an accepted
+// boundary, |d| <= tol_phi, |g| <= tol_f = tol_phi beta / alpha, dies out in the fed-back state, but what it adds to phi_multiplied on the way stays:
+// both differences end at 0 under the linear loop, which fixes the sums over the transient: g + beta sum(err) = 0 and d + sum(freq) + alpha
+// sum(err) = 0, so sum(err) = -g / beta, sum(freq) = -d + g alpha / beta, and phi_multiplied = sum(mult freq + alpha err) moves by
+// -mult d + (mult - 1) g alpha / beta: at most (|mult| + |mult - 1|) tol_phi per accepted boundary.  Its distance from the serial loop
+// therefore grows with the number of accepted boundaries (the stream length) and with the multiplier; it is a random walk where the input carries
+// noise and a straight line where it does not (every lane then misses the long-running trajectory by the same amount: the floor below).
+// Measured on the CPU against the serial loop, unit-test loop, segments of 64: carrier + 0.1 noise, mult 20: 4e-7 after 2^15 samples, 7.8e-7
+// after 2^16 and still rising (1.1e-6 with another noise seed); mult 3: 6e-8 .. 1.8e-7 throughout.  "speculate=0" gives the serial value at any length.
+//
 // Why this works: the phase detector is an exact atan2, so two trajectories over the same input whose wraps and clamps coincide differ by a
 // quantity that evolves under the linearised loop z^2 + (alpha + beta - 2) z + (1 - alpha): it shrinks by the larger root modulus r per sample.
 // A lane started W samples early from the INITIAL state therefore arrives at its segment with the true state up to 2 pi r^W - when the loop
@@ -16,7 +26,7 @@
 //             the CPU on the stereo pilot loop, the AM-synchronous loop and the unit-test loop; tools/host_pll_check.hip prints the largest entry
 //             error it sees).  A tolerance at the floor would reject everything; 2^-22 is 12 x the top of the floor.  Ceiling: the golden tests hold
 //             the output within 1e-6 of the f64 model; a boundary perturbation d moves cis(phi) by at most |d| while the loop pulls it back, and
-//             2^-22 leaves a factor 4 for the Float32 rounding of the output (6e-8) and the residue in phi_multiplied.
+//             2^-22 leaves a factor 4 for the Float32 rounding of the output (6e-8).  (phi_multiplied is not covered by this: see above.)
 //   tol_f   = tol_phi * beta / alpha: the frequency error the loop filter makes of a phase error tol_phi (freq += beta err, phi += alpha err).
 //   lock    = a segment is accepted only if the mean of |err| over its samples is at most pi / 4: halfway between perfect lock (0) and none (err
 //             uniform over (-pi, pi], mean pi / 2; a 64-sample mean of that is 1.57 +- 0.11, seven deviations away).  The floor above is the spacing
@@ -24,6 +34,19 @@
 //             trajectories that have converged still differ by ~1e-7 (measured): they would pass tol_phi now and then, by chance rather than with the
 //             margin it was chosen for.  Such segments are rerun serially: out of lock the stage IS the serial loop.  (A maximum of |err| instead of
 //             the mean would reject 4e-4 of the samples of a locked pilot in 0.3 noise, a tenth of its 256-sample segments.)
+//   floor   = a segment is accepted only if the mean of |err| over its samples is at least PLL_LOCK_FLOOR = 1e-5 rad.  Under it the input carries no
+//             dither: err sits inside the Float32 rounding of the VCO sample (a dead zone of ~6e-8 rad), two trajectories that have come that close
+//             see the same err and stop converging, so every lane (W .. W + C samples old) differs from the long-running trajectory by the same tiny
+//             (d, g), and phi_multiplied integrates it over every boundary: on a noise-free carrier at the loop's centre, 2^16 samples, segments
+//             of 64, the out port was 3.4e-6 (mult 3), 4.8e-6 (mult -2), 3.1e-5 (mult 20) from the serial loop with nothing rejected.
+//             The sweep behind the value (CPU, unit-test loop at mult 3, carrier at 0.1 + sigma complex noise, 2^16 samples, no floor; largest
+//             out difference from the serial loop, and the mean |err| in lock):
+//               sigma 0     1e-9    1e-8    1e-7    1e-6    1e-5    1e-4    1e-3    1e-2    1e-1
+//               out   3.4e-6 2.2e-6 4.0e-7  3.0e-7  2.2e-7  1.2e-7  1.2e-7  1.2e-7  1.5e-7  1.8e-7
+//               |err| 1e-12  2e-10  1.1e-8  8.4e-8  8.3e-7  8.3e-6  8.3e-5  8.3e-4  8.3e-3  8.3e-2
+//             The drift is under a quarter of the 1e-6 bar (2.5e-7) from sigma = 1e-6, mean |err| 8.3e-7; the floor is a decade above that.
+//             Segments under it are rerun serially, so a synthetic tone without dither gets the serial loop's values at single-lane speed;
+//             input with sigma = 1e-4 of noise on a unit carrier (80 dB under it) and more speculates as before.
 //   tol_w   = tol_phi / 256: the warm-up ends where the linear model has shrunk the worst initial error (2 pi) to 2^-30, far under the floor, so
 //             a rejection means "not in lock", not "warm-up a little short".  W = ceil(ln(tol_w / 2 pi) / ln r).
 #pragma once
@@ -40,6 +63,7 @@ namespace lrhip {
 constexpr double PLL_TWO_PI = 6.283185307179586476925286766559;      // 2 * math.pi
 constexpr double PLL_TOL_PHI = 1.0 / 4194304.0;                       // 2^-22 rad
 constexpr double PLL_LOCK_ERR = 0.78539816339744831;                  // pi / 4: the largest mean |err| of a segment in lock
+constexpr double PLL_LOCK_FLOOR = 1e-5;                               // the smallest mean |err| at which a speculated entry can be verified
 constexpr unsigned long PLL_MIN_SEGMENT = 64;
 
 struct PllParams { double alpha, beta, fmin, fmax, mult; };
@@ -88,10 +112,11 @@ LR_PLL_HD inline bool pll_agree(const PllEdge &entry, const PllEdge &exit_prev, 
     return fabs(d) <= tol_phi && fabs(entry.fl - exit_prev.fl) <= tol_f;
 }
 
-// segment k as a whole: its entry agrees with the predecessor's exit and the loop stayed in lock over it (emean: the segment's mean |err|)
+// segment k as a whole: its entry agrees with the predecessor's exit, the loop stayed in lock over it and the input carried enough dither for
+// the agreement to mean something (emean: the segment's mean |err|; a NaN is rejected)
 LR_PLL_HD inline bool pll_accept(const PllEdge &entry, const PllEdge &exit_prev, double emean, double tol_phi, double tol_f)
 {
-    return pll_agree(entry, exit_prev, tol_phi, tol_f) && emean <= PLL_LOCK_ERR;
+    return pll_agree(entry, exit_prev, tol_phi, tol_f) && emean <= PLL_LOCK_ERR && emean >= PLL_LOCK_FLOOR;
 }
 
 // the larger root modulus of z^2 + (alpha + beta - 2) z + (1 - alpha)

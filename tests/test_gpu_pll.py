@@ -1,6 +1,7 @@
 """PLLBlock on the MI355X against the f64 model of pll.lua (tests/helpers/pll_model.py): the speculative path in lock (no repair, Chain.last_launches
 = 4), the repair walk (5), the serial path (1), replay consistency where the loop is chaotic or sits on its clamp, the edges of the segment grid,
-reset, NaN, refused parameters and time partitions, and the two receivers that wait on the PLL against the same topology built from the oracle."""
+reset, NaN, refused parameters and time partitions, the streams of tests/helpers/pll_signals.py that are repaired in part, run a negative loop or
+multiplier, or carry no noise, and the two receivers that wait on the PLL against the same topology built from the oracle."""
 import functools
 import math
 
@@ -11,6 +12,7 @@ import luaradio_amd as lr
 from luaradio_amd import _lib, types
 from luaradio_amd import blocks as B
 from tests.helpers import pll_model as M
+from tests.helpers import pll_signals as S
 
 pytestmark = pytest.mark.gpu
 
@@ -197,6 +199,119 @@ def test_time_partitions_are_refused():
         ch.halo()
     with pytest.raises(lr.LrhipError):
         ch.start_at(100000)
+
+
+# ---- the streams of tests/helpers/pll_signals.py: tests/test_pll_cpu.py asserts on the CPU that each takes the path it was built for -------------
+PARTIAL_CUTS = (0, 1, 30500, 30501, 31990, 40000)      # a boundary inside the burst, state carried out of a repaired run, serial calls in between
+SIGNAL_LOOPS = {"negative": (S.NEGATIVE_LOOP, 2.0), "pilot": (S.PILOT_LOOP, S.PILOT_RATE)}
+
+
+@functools.lru_cache(maxsize=None)
+def signal_model(name, mult, n=None):
+    loop, rate = SIGNAL_LOOPS.get(name, (S.LOOP, 2.0))
+    out, err, states = M.run(getattr(S, name)()[:n], *loop, mult, rate=rate)
+    for a in (out, err, states):
+        a.setflags(write=False)
+    return out, err, states
+
+
+def compare(what, got, want):
+    """prints the largest difference and, where it is over the bar, the first sample over it; then asserts the bar"""
+    d = np.abs(got.astype(np.complex128) - want.astype(np.complex128))
+    worst = float(d.max()) if len(d) else 0.0
+    over = np.flatnonzero(d > EPS)
+    print("%s: %.3g%s" % (what, worst, "" if not len(over) else " (first over the bar: sample %d, got %r, model %r; last: %d; %d in all)" % (
+        over[0], got[over[0]], want[over[0]], over[-1], len(over))))
+    assert len(got) == len(want) and worst <= EPS
+
+
+def both_ports(name, mult, knobs="", n=None, launches=None, cuts=None):
+    loop, rate = SIGNAL_LOOPS.get(name, (S.LOOP, 2.0))
+    x = getattr(S, name)()[:n]
+    got = {}
+    for pname, want in zip(("out", "error"), signal_model(name, mult, n)[:2]):
+        ch = lr.Chain([port(pname, mult, knobs, loop, rate)])
+        got[pname] = ch.process(x) if cuts is None else ragged(ch, x, tuple(cuts) + (len(x),))
+        if launches is not None:
+            assert ch.last_launches == launches, (pname, ch.last_launches)
+        compare("%s x%g %s%s %s" % (name, mult, knobs or "default plan", "" if cuts is None else " ragged", pname), got[pname], want)
+    return got
+
+
+@pytest.mark.parametrize("name", ["burst", "gap", "early_and_late"])
+def test_partial_repair(name):
+    """Lock lost and regained inside one call: the walk starts in mid-stream, stops, and the segments behind it stay speculated (CPU: 32, 35 and 18
+    of 1024 segments rerun; in `gap` one is re-accepted from its speculated entry behind a repaired one; in `early_and_late` segment 1 and the
+    37-sample last segment are rerun).  Then in calls cut inside the burst."""
+    both_ports(name, 3.0, ":segment=64", launches=REPAIRED)
+    both_ports(name, 3.0, "", launches=REPAIRED)
+    got = both_ports(name, 3.0, ":segment=64", cuts=PARTIAL_CUTS)
+    if name == "gap":
+        # exact zeros: x * conj(vco) is (+-0, +-0), and atan2(+0, -0) = pi where the VCO sample has a negative real and a non-negative imaginary
+        # part of its conjugate.  The model meets the case, and the device answers it the same way, sample for sample.
+        pi32, want = np.float32(math.pi), signal_model(name, 3.0)[1]
+        inside = slice(*S.BURST)
+        assert int(np.sum(want[inside] == pi32)) > 0 and not np.any(want[inside] == -pi32)
+        assert set(np.unique(want[inside]).tolist()) <= {0.0, float(pi32)}
+        assert np.array_equal(got["error"][inside] == pi32, want[inside] == pi32)
+
+
+def test_phase_jump_stays_speculated():
+    """a 2 rad step of the carrier's phase: a transient that every lane sees with the same history, so nothing is rejected"""
+    err = signal_model("jump", 3.0)[1]
+    assert float(np.max(np.abs(err[40003:40010]))) > 1.5 and float(np.max(np.abs(err[39000:40003]))) < 0.6       # the step is there
+    both_ports("jump", 3.0, ":segment=64", launches=SPECULATED)
+    both_ports("jump", 3.0, "", launches=SPECULATED)
+
+
+def test_negative_loop_and_negative_multiplier():
+    """the < -2 pi wrap branches of pll_step: phi_locked running downward (a loop over -0.21 .. -0.19), and phi_multiplied running downward while
+    phi_locked runs upward (mult = -2)"""
+    states = signal_model("negative", 3.0)[2]
+    assert int(np.sum(np.diff(states[:, 0]) > math.pi)) > 1000 and int(np.sum(np.diff(states[:, 0]) < -math.pi)) == 0
+    assert int(np.sum(np.diff(states[:, 1]) > math.pi)) > 1000
+    both_ports("negative", 3.0, ":segment=64", launches=SPECULATED)
+    both_ports("negative", 3.0, ":segment=64", cuts=CUTS[:-1])
+    states = signal_model("locked", -2.0)[2]
+    assert int(np.sum(np.diff(states[:, 0]) < -math.pi)) > 1000 and int(np.sum(np.diff(states[:, 1]) > math.pi)) > 1000
+    both_ports("locked", -2.0, ":segment=64", launches=SPECULATED)
+    both_ports("locked", -2.0, ":segment=64", cuts=CUTS[:-1])
+
+
+def test_more_than_a_turn_per_sample():
+    """mult = 20: phi_multiplied gains 12.6 rad per sample, the single conditional wrap takes off 6.28, and the value grows without bound (the
+    reference's behaviour).  2^15 samples: phi_multiplied's distance from the serial loop grows with the stream (pll_plan.h; on the CPU 4e-7 here,
+    7.8e-7 at 2^16 and rising), so this is the longest stream the bar is asserted on."""
+    n = 1 << 15
+    assert float(signal_model("locked", 20.0, n)[2][-1, 1]) > 1e5
+    both_ports("locked", 20.0, ":segment=64", n=n, launches=SPECULATED)
+    both_ports("locked", 20.0, ":segment=64", n=n, cuts=[c for c in CUTS if c < n])
+
+
+def test_the_receivers_pilot_loop():
+    """PLLBlock(100, 18950, 19050, 2) at 220 500 Hz, W = 5 957: a whole call of 2^16 speculates (W + 2 C <= n / 2); ragged, the calls shorter than
+    2 (W + 2 C) run serially in between"""
+    both_ports("pilot", 2.0, "", launches=SPECULATED)
+    both_ports("pilot", 2.0, "", cuts=CUTS[:-1])
+
+
+@pytest.mark.parametrize("mult", [1.0, 3.0, -2.0])
+@pytest.mark.parametrize("name", ["clean_centre", "clean_off"])
+def test_clean_carriers_do_not_drift(name, mult):
+    """No noise: the mean |err| is under PLL_LOCK_FLOOR, the segments are rerun serially, and phi_multiplied does not drift away from the model
+    (before the floor, on the CPU: 3.4e-6 at mult 3 and 4.8e-6 at mult -2 on clean_centre, linear in time, with nothing rejected)."""
+    both_ports(name, mult, ":segment=64", launches=REPAIRED)
+
+
+def test_reset_after_a_repaired_call():
+    x = S.burst()
+    for name in ("out", "error"):
+        blk = port(name, 3.0, ":segment=64")
+        first = blk.process(x)
+        blk.reset()
+        again = blk.process(x)
+        assert np.array_equal(first.view(np.uint8), again.view(np.uint8))
+        compare("burst after reset %s" % name, again, signal_model("burst", 3.0)[0 if name == "out" else 1])
 
 
 # ---- the receivers that waited on the PLL, against the same topology from the oracle's block functions and the PLL model ------------------------

@@ -5,9 +5,11 @@
 // accepted everywhere and stay within 1e-6 of the serial loop, that a short warm-up, pure noise and a carrier outside the clamp range end in the
 // repair walk and are still consistent
 // (a replay of the recurrence driven by the produced error samples reproduces out and error within 1e-6), and that a NaN terminates the walk.
+// With arguments (play_file below) it plays one call over a raw ComplexFloat32 file instead: tests/test_pll_cpu.py feeds it tests/helpers/pll_signals.py.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 #include "pll_plan.h"
 using namespace lrhip;
@@ -48,7 +50,7 @@ static std::vector<float> tone(unsigned long n, double w, double ph, double sigm
     return x;
 }
 
-struct Result { std::vector<float> out, err; unsigned long long rejected = 0, repaired = 0; double entry_err = 0.0; PllState last; PllPlan plan; };
+struct Result { std::vector<float> out, err; std::vector<unsigned char> bad; unsigned long long rejected = 0, repaired = 0; double entry_err = 0.0; PllState last; PllPlan plan; };
 
 // one call of the stage as the host-side run() and the kernels perform it
 static Result play(const std::vector<float> &x, const PllParams &p, unsigned long W, unsigned long lanes, unsigned long seg, bool allow, PllState carried)
@@ -83,6 +85,7 @@ static Result play(const std::vector<float> &x, const PllParams &p, unsigned lon
         r.last = pll_emit_lane<PLL_PORT_OUT>(x.data(), n, p, q.C, k, entry.data(), pm.data(), r.out.data());
         (void)pll_emit_lane<PLL_PORT_ERROR>(x.data(), n, p, q.C, k, entry.data(), pm.data(), r.err.data());
     }
+    r.bad = bad;                                 // after the walk: the segments that were rerun serially
     return r;
 }
 
@@ -134,8 +137,39 @@ static void locked_case(const char *what, const PllParams &p, const std::vector<
     CHECK(a.entry_err < PLL_TOL_PHI / 4, "%s: entry error %.2e is not well under the tolerance", what, a.entry_err);
 }
 
-int main()
+// The second mode: one call of the stage over a raw ComplexFloat32 file, against the serial path of the same code.
+//   host_pll_check FILE BANDWIDTH FMIN FMAX MULT RATE [SEGMENT]
+// prints nseg, rejected, repaired, whether the last segment was repaired, and the largest out / error difference in each quarter of the stream
+static int play_file(int argc, char **argv)
 {
+    if (argc < 7) { fprintf(stderr, "usage: %s FILE BANDWIDTH FMIN FMAX MULT RATE [SEGMENT]\n", argv[0]); return 2; }
+    FILE *f = fopen(argv[1], "rb");
+    if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
+    std::vector<float> x;
+    float buf[4096];
+    for (size_t got; (got = fread(buf, sizeof(float), 4096, f)) > 0;) x.insert(x.end(), buf, buf + got);
+    fclose(f);
+    if (x.size() % 2) { fprintf(stderr, "%s: not a whole number of ComplexFloat32 samples\n", argv[1]); return 2; }
+    const PllParams p = make_params(atof(argv[2]), atof(argv[3]), atof(argv[4]), atof(argv[5]), atof(argv[6]));
+    const unsigned long seg = argc > 7 ? strtoul(argv[7], nullptr, 10) : 0, n = x.size() / 2;
+    const unsigned long W = pll_warmup(p.alpha, p.beta, PLL_TOL_PHI / 256.0);
+    const Result a = play(x, p, W, 131072, seg, true, pll_initial(p)), s = play(x, p, W, 131072, seg, false, pll_initial(p));
+    printf("n %lu W %lu C %lu speculate %d nseg %lu rejected %llu repaired %llu last_repaired %d\n", n, W, a.plan.C, (int)a.plan.speculate, a.plan.nseg,
+           a.rejected, a.repaired, (int)(a.plan.speculate && a.bad[a.plan.nseg - 1]));
+    double d_out[4], d_err[4];
+    for (int q = 0; q < 4; q++) {
+        const unsigned long i0 = n * q / 4, i1 = n * (q + 1) / 4;
+        d_out[q] = max_diff(std::vector<float>(a.out.begin() + 2 * i0, a.out.begin() + 2 * i1), std::vector<float>(s.out.begin() + 2 * i0, s.out.begin() + 2 * i1));
+        d_err[q] = max_diff(std::vector<float>(a.err.begin() + i0, a.err.begin() + i1), std::vector<float>(s.err.begin() + i0, s.err.begin() + i1), true);
+    }
+    printf("out %.3e %.3e %.3e %.3e\n", d_out[0], d_out[1], d_out[2], d_out[3]);
+    printf("error %.3e %.3e %.3e %.3e\n", d_err[0], d_err[1], d_err[2], d_err[3]);
+    return 0;
+}
+
+int main(int argc, char **argv)
+{
+    if (argc > 1) return play_file(argc, argv);
     Rng g;
     // ---- W against the pole radius, for the three loops the tolerances were chosen on
     const PllParams unit = make_params(0.01, 0.19, 0.21, 3.0, 2.0), pilot = make_params(100, 18950, 19050, 2.0, 220500.0), am = make_params(1000, 4900, 5100, 1.0, 44100.0);
