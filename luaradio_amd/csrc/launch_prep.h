@@ -1,5 +1,4 @@
 // launch_prep.h - what a launch settles before it goes: the kernel's dynamic-LDS limit, its resident workgroups per CU, the grid of a persistent kernel.
-// (The overlap-save launches of stage_fir.h and the single-launch receiver of stage_rx.h still prepare their kernels per stage, by hand.)
 #pragma once
 #include "common.h"
 

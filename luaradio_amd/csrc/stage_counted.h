@@ -36,6 +36,17 @@ template <class S, int BYTES = 0> struct Carried {
     }
 };
 
+// The same pair of alternating slots for a stage that sizes and fills them itself (FirStage's history, discriminator sample and recurrence
+// state): in() is what a call reads, out() what its kernels write, flip() makes that the next call's input.
+struct TwoSlots {
+    DeviceBuf slot[2];
+    int cur = 0;
+    int reset(size_t bytes) { cur = 0; return (zero_fill(slot[0], bytes) || zero_fill(slot[1], bytes)) ? -1 : 0; }
+    void *in() const { return slot[cur].p; }
+    void *out() const { return slot[cur ^ 1].p; }
+    void flip() { cur ^= 1; }
+};
+
 // ---- a call's scratch, carved into typed regions in the order they are taken, each aligned to its element type
 template <class T> struct Region {
     size_t at = 0;

@@ -103,14 +103,13 @@ struct HilbertStage : lrhip_stage {
         static const bool two_pass = getenv("LRHIP_HILBERT_TWO_PASS") != nullptr;      // A/B knob: filter, then combine (round 2)
         if (!two_pass && fir->hilbert_ok() && ((uintptr_t)in_dev % 4) == 0) {
             // one launch: the filter's epilogue writes (delayed input, filtered input) pairs (hilberttransform.lua:107-124 is one loop as well)
-            if (fir->launch_hilbert((const float *)in_dev, (long)n, (float *)out_dev)) return -1;
+            if (fir->hilbert((const float *)in_dev, (long)n, (float *)out_dev)) return -1;
             return (long)n;
         }
         if (tmp.reserve(n * sizeof(float))) return -1;
+        const float *old_hist = fir->h_in();      // the history that is current for this chunk: core() makes the next one current
         long got = fir->core((const float *)in_dev, (long)n, (float *)tmp.p, n);
         if (got < 0) return got;
-        // core() has swapped the ping-pong history: the history that was current for this chunk is the other one
-        const float *old_hist = (const float *)fir->hist[fir->cur ^ 1].p;
         unsigned grid = grid_for(n, 256);
         hipLaunchKernelGGL(hilbert_combine_kernel, dim3(grid), dim3(256), 0, ctx().stream, old_hist, (const float *)in_dev, (const float *)tmp.p,
                            (float2 *)out_dev, n, fir->M);

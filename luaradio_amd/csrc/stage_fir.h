@@ -35,11 +35,21 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         return h;
     }
     DeviceBuf d_taps, d_atab, d_ctaps4;
+    // ---- carried from call to call: the history, the discriminator's previous sample, the fused recurrence's state, the decimation index and the absolute
+    // sample count.  A launch reads the *_in() slots and writes the *_out() ones; commit() alone advances any of it (reset() and seek() set it)
     int hist_pad = 0;                     // leading pad floats in the history buffers (1 for complex taps, see launch_mfma_cc)
-    DeviceBuf hist[2];
-    int cur = 0;
+    TwoSlots hist, disc, iir;             // (M - 1) S floats behind the pad; one float2; four floats
     unsigned long index = 0;              // carried downsampler index (downsampler.lua:53)
     uint64_t rot_step = 0, count = 0;     // absolute index of the next input sample
+    const float *h_in() const { return (const float *)hist.in() + hist_pad; }
+    float *h_out() const { return M > 1 ? (float *)hist.out() + hist_pad : nullptr; }      // (one tap: nothing to carry)
+    const float2 *disc_in() const { return (const float2 *)disc.in(); }
+    float2 *disc_out() const { return (float2 *)disc.out(); }
+    const float *iir_in() const { return (const float *)iir.in(); }
+    float *iir_out() const { return (float *)iir.out(); }
+    // what a launch_* / dispatch_* returns: -1 with the message set, or which of the next slots its launches wrote
+    enum : int { WROTE_HIST = 1, WROTE_DISC = 2, WROTE_IIR = 4 };
+    static int wrote_hist(const float *ho) { return ho ? WROTE_HIST : 0; }
     // overlap-save emission framing (firfilter.lua:451-485)
     long L = 0, fill = 0;
     DeviceBuf pending, work;
@@ -52,11 +62,9 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     DeviceBuf d_fft_tables;
     DeviceBuf d_fft4k_tables;             // 513 .. 1281 taps on a ComplexFloat32 stream: the 4096-point kernel (kernels_firfft4k.h)
     DeviceBuf d_fft64_tables;             // ... and its one-wave-per-block form (kernels_firfft64.h)
-    int fft_blocks_per_cu = 0;
     int mode_req = 0;                     // use_fft as the caller passed it (0..3), before 3 = automatic was resolved
     DeviceBuf d_dec_tables;
     double rot_omega = 0.0;
-    bool hist_in_kernel = false;          // set by a launch that also wrote the next history buffer
     int post_unary = 0;      // 1 + UN_CMAG / UN_CPHASE / UN_CREAL / UN_CIMAG folded into the LDS-staged decimator's store (chains: tuner -> ComplexMagnitude ...), Float32 out
     DeviceBuf edge;
     // fix-up of the wave-first discriminator outputs (disc_epilogue): done by fir_disc_fixup_kernel, or - defer_fixup - left to the next
@@ -67,8 +75,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     const float2 *fix_prev_ptr = nullptr;
     FirStage *fix_src = nullptr;           // consumer side: the stage whose edge records are to be applied
     double disc_gain = 1.0;
-    DeviceBuf disc_prev;
-    int disc_cur = 0;
 
     const char *kind() const override { return "fir"; }
     unsigned long max_output(unsigned long n) const override
@@ -78,12 +84,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     }
     int reset() override
     {
-        cur = 0; index = 0; count = 0; fill = 0; disc_cur = 0; iir_cur = 0;
-        if (iir_fused && (zero_fill(iir_state[0], 4 * sizeof(float)) || zero_fill(iir_state[1], 4 * sizeof(float)))) return -1;
-        if ((pre_disc || post_disc) && zero_fill(disc_prev, 4 * sizeof(float))) return -1;
-        size_t hb = ((size_t)(M > 1 ? M - 1 : 1) * S + hist_pad) * sizeof(float);
-        if (zero_fill(hist[0], hb) || zero_fill(hist[1], hb)) return -1;
-        return 0;
+        index = 0; count = 0; fill = 0;
+        if (iir_fused && iir.reset(4 * sizeof(float))) return -1;
+        if ((pre_disc || post_disc) && disc.reset(sizeof(float2))) return -1;
+        return hist.reset(((size_t)(M > 1 ? M - 1 : 1) * S + hist_pad) * sizeof(float));
     }
 
     int seek(unsigned long long n0, unsigned long long *n0_out) override
@@ -124,31 +128,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         else return set_error("internal: no persistent Toeplitz kernel at decimation %d", DD);
     }
 
-    // The overlap-save launches (launch_fft, launch_fft64, launch_fft64_long) keep their own preparation, per stage
-    template <typename K>
-    int prepare_kernel(K kern, size_t lds_bytes, int *blocks_per_cu, int threads = 256)
-    {
-        if (lds_bytes > 48 * 1024) LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        if (blocks_per_cu) {
-            int nb = 0;
-            LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds_bytes));
-            *blocks_per_cu = nb < 1 ? 1 : nb;
-        }
-        return 0;
-    }
-    std::vector<std::pair<const void *, int>> prepared;
-    template <typename K>
-    int prepared_blocks(K kern, size_t lds_bytes, int threads = 256)
-    {
-        const void *kp = (const void *)kern;
-        for (const auto &e : prepared)
-            if (e.first == kp) return e.second;
-        int nb = 0;
-        if (prepare_kernel(kern, lds_bytes, &nb, threads)) return -1;
-        prepared.emplace_back(kp, nb);
-        return nb;
-    }
-
     template <int SS, int DD, int NACC, int KS, int NW = 4>
     int launch_mfma_ks(const float *x, long n, float *y, long n_out)
     {
@@ -170,9 +149,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         size_t lds_bytes = lds_floats * sizeof(float);
         long ntiles = (n_out + TILE_OUT - 1) / TILE_OUT;
         const float *atab = (const float *)d_atab.p;          // zero-padded reversed taps
-        const float *h = (const float *)hist[cur].p + hist_pad;
+        const float *h = h_in();
         int out_aligned = ((uintptr_t)y % 16) == 0;
         uint64_t rs = rot ? rot_step : 0, rc = rot ? count : 0;
+        float *ho = KS > 0 ? h_out() : nullptr;      // the persistent kernels write the next history, the generic one leaves it to commit()
         if constexpr (KS > 0) {
             auto launch = [&](auto kern) -> int {
                 const long slots = chip_slots(kern, 64 * NW, lds_bytes);
@@ -180,10 +160,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                 const int rounds = persistent_rounds(ntiles, slots, fir_knobs().fir_rounds);      // tile order (LRHIP_FIR_ROUNDS)
                 const unsigned grid = persistent_grid(ntiles, slots, rounds);
                 if (post_disc && edge.reserve((size_t)ntiles * 2 * NW * sizeof(float2))) return -1;
-                float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
                 hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds_bytes, ctx().stream, h, x, atab, y, M, n, n_out, (long)index, e,
-                                   ntiles, out_aligned, rs, rc, (float2 *)edge.p, post_disc ? (float2 *)disc_prev.p + (disc_cur ^ 1) : nullptr, 1.0 / disc_gain, ho, rounds);
-                hist_in_kernel = ho != nullptr;
+                                   ntiles, out_aligned, rs, rc, (float2 *)edge.p, post_disc ? disc_out() : nullptr, 1.0 / disc_gain, ho, rounds);
                 return 0;
             };
             int rc2;
@@ -201,7 +179,6 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                              : rel_rot ? launch(fir_mfma_persistent_kernel<2, DD, NACC, true, KS, 1, true>) : launch(fir_mfma_persistent_kernel<2, DD, NACC, true, KS, 1, false>);
                     if (rc2) return rc2;
                     LR_LAUNCH_CHECK();
-                    float2 *dp = (float2 *)disc_prev.p;
                     // records per unit of FIX_UNIT outputs: a wave's range in the in-register epilogue, a whole tile in the LDS one
                     constexpr int FIX_UNIT = LRHIP_DISC_EPI_LDS ? TILE_OUT : TILE_OUT / NW;
                     const long nunits = LRHIP_DISC_EPI_LDS ? ntiles : NW * ntiles;
@@ -209,16 +186,15 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                     if (defer_fixup && (FIX_UNIT & (FIX_UNIT - 1)) == 0 && FIX_UNIT >= 256) {
                         fix_ready = true;
                         fix_nunits = nunits; fix_unit = FIX_UNIT;
-                        fix_prev_ptr = (const float2 *)(dp + disc_cur);
+                        fix_prev_ptr = disc_in();
                         fix_shift = 0;
                         while ((1 << fix_shift) < FIX_UNIT) fix_shift++;
                     } else {
                         hipLaunchKernelGGL(fir_disc_fixup_kernel, dim3((unsigned)((nunits + 255) / 256)), dim3(256), 0, ctx().stream, (const float2 *)edge.p,
-                                           nunits, FIX_UNIT, y, n_out, (const float2 *)(dp + disc_cur), 1.0 / disc_gain);
+                                           nunits, FIX_UNIT, y, n_out, disc_in(), 1.0 / disc_gain);
                         LR_LAUNCH_CHECK();
                     }
-                    disc_cur ^= 1;
-                    return 0;
+                    return wrote_hist(ho) | WROTE_DISC;
                 }
             }
             if (post_disc) return set_error("internal: discriminator epilogue without a persistent kernel variant");
@@ -230,7 +206,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                     rc2 = rot ? raw(std::true_type{}) : raw(std::false_type{});
                     if (rc2) return rc2;
                     LR_LAUNCH_CHECK();
-                    return 0;
+                    return wrote_hist(ho);
                 }
             }
             if (raw_now) return set_error("internal: raw records reached a kernel without a record instantiation");
@@ -254,11 +230,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             if (rc2) return rc2;
         }
         LR_LAUNCH_CHECK();
-        return 0;
+        return wrote_hist(ho);
     }
 
-    // HilbertTransformBlock in one launch (hilbert_ok): the generic Float32 Toeplitz kernel with the pair epilogue (kernels_fir.h, HILB).  y2 receives n
-    // ComplexFloat32 samples (delayed input, filtered input); history / index bookkeeping is core()'s (D = 1: index stays 0)
+    // HilbertTransformBlock in one launch (hilbert_ok; hilbert() below).  y2 receives n ComplexFloat32 samples (delayed input, filtered input)
     // the window form (kernels_firwin.h hilbert_win_kernel): the reference's tap counts, taps at even distance from the centre exactly zero
     int hilb_sparse = -1;
     template <int MM>
@@ -272,21 +247,13 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         long run = (ntiles + 4 * slots - 1) / (4 * slots);
         if (fir_knobs().hilbert_run > 0) run = fir_knobs().hilbert_run;      // A/B knob: tiles per workgroup
         const unsigned grid = (unsigned)((ntiles + run - 1) / run);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float *)d_taps.p, y2, n, run,
-                           (float *)hist[cur ^ 1].p + hist_pad);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h_in(), x, (const float *)d_taps.p, y2, n, run, h_out());
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        count += (uint64_t)n;
-        return 0;
+        return WROTE_HIST;
     }
-    int launch_hilbert(const float *x, long n, float *y2)
+    // the generic Float32 Toeplitz kernel with the pair epilogue (kernels_fir.h, HILB); the history is left to commit()
+    int launch_hilbert_mfma(const float *x, long n, float *y2)
     {
-        if (hilb_sparse < 0) {
-            hilb_sparse = (M == 65 || M == 129) ? 1 : 0;
-            for (int j = 0; j < M && hilb_sparse; j += 2)
-                if (taps_rev[(size_t)j] != 0.0f) hilb_sparse = 0;
-        }
-        if (hilb_sparse && !fir_knobs().hilbert_mfma && index == 0) return M == 65 ? launch_hilbert_win<65>(x, n, y2) : launch_hilbert_win<129>(x, n, y2);
         constexpr int NACC = 4;
         using G = FirMfmaGeom<1, 1>;
         constexpr int TILE_OUT = G::tile_out(NACC);
@@ -298,17 +265,9 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const long ntiles = (n + TILE_OUT - 1) / TILE_OUT;
         auto kern = fir_mfma_kernel<1, 1, NACC, false, 1, true>;
         if (kernel_allow_lds(kern, lds_bytes)) return -1;
-        hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float *)d_atab.p, y2, M, n, n,
+        hipLaunchKernelGGL(kern, dim3((unsigned)ntiles), dim3(256), lds_bytes, ctx().stream, h_in(), x, (const float *)d_atab.p, y2, M, n, n,
                            (long)index, e, ksteps, (int)(((uintptr_t)y2 % 16) == 0), (uint64_t)0, (uint64_t)0);
         LR_LAUNCH_CHECK();
-        // history carry, as core() does for kernels that do not write it themselves
-        if (M > 1) {
-            unsigned grid = grid_for((unsigned long)(M - 1), 256);
-            hipLaunchKernelGGL(fir_history_kernel<1>, dim3(grid), dim3(256), 0, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (float *)hist[cur ^ 1].p + hist_pad, M, n);
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-        }
-        count += (uint64_t)n;
         return 0;
     }
 
@@ -329,7 +288,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         size_t lds_bytes = ((size_t)2 * fir_taps_len(DD2, ksteps) + (size_t)G::phys(span) + G::PAD + 8) * sizeof(float);
         long ntiles = (n_out + TILE_OUT - 1) / TILE_OUT;
         const float *atab = (const float *)d_atab.p;          // [re taps | im taps], each zero-padded
-        const float *h = (const float *)hist[cur].p;          // includes the pad float
+        const float *h = h_in() - hist_pad;                   // includes the pad float
         int out_aligned = ((uintptr_t)y % 16) == 0;
         auto kern = fir_mfma_kernel<1, DD2, NACC, false, 2>;
         if (kernel_allow_lds(kern, lds_bytes)) return -1;
@@ -360,11 +319,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         const long nblocks = (n_out + Lf - 1) / Lf, nslots = (nblocks + NG - 1) / NG, slots = chip_slots(kern, 256 * NG, lds_bytes);
         if (slots < 0) return -1;
         const unsigned grid = persistent_grid(nslots, slots, 0);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * NG), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft4k_tables.p, y, M, n,
-                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, fir_knobs().f4k_xcd_map);      // (XCD-major block order)
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * NG), lds_bytes, ctx().stream, h_in(), x, (const float2 *)d_fft4k_tables.p, y, M, n,
+                           n_out, nblocks, h_out(), fir_knobs().f4k_xcd_map);      // (XCD-major block order)
         LR_LAUNCH_CHECK();
-        hist_in_kernel = true;
-        return 0;
+        return WROTE_HIST;
     }
     // one WAVE per 4096-point block as 64 x 64 (kernels_firfft64.h): eight waves per CU with the conjugate-symmetric H of real taps, four with complex taps
     template <int VV, int WAVES, int SS = 2, bool HG = false>
@@ -373,15 +331,14 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         constexpr long Lf = F4K_N - VV;
         const size_t lds_bytes = (size_t)f64_lds_elems(WAVES) * sizeof(float2);
         auto kern = fir_fft64_kernel<VV, WAVES, 1, SS, HG>;
-        if (prepared_blocks(kern, lds_bytes, 64 * WAVES) < 0) return -1;
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         // (Float32 stream: two stream blocks per transform - the kernel's block count is the number of transforms)
         const long nblocks = ((n_out + Lf - 1) / Lf + (2 - SS)) / (3 - SS), nslots = (nblocks + WAVES - 1) / WAVES;
         const unsigned grid = (unsigned)(nslots < ctx().num_cus ? nslots : ctx().num_cus);      // 108 / 158 KB of LDS: one workgroup per CU
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft64_tables.p, y, M, n,
-                           n_out, nblocks, M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, fir_knobs().f4k_xcd_map, 0L, 0);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds_bytes, ctx().stream, h_in(), x, (const float2 *)d_fft64_tables.p, y, M, n,
+                           n_out, nblocks, h_out(), fir_knobs().f4k_xcd_map, 0L, 0);
         LR_LAUNCH_CHECK();
-        hist_in_kernel = true;
-        return 0;
+        return WROTE_HIST;
     }
     // round 5: V = 2 048, one partition (eight waves on real taps, four on complex ones) or two (four waves, a run of consecutive blocks per wave)
     template <int NP, int SS = 2>
@@ -391,19 +348,20 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         constexpr long Lf = F4K_N - VV;
         const size_t lds_bytes = (size_t)f64_lds_elems(WAVES, NP) * sizeof(float2);
         auto kern = fir_fft64_kernel<VV, WAVES, NP, SS>;
-        if (prepared_blocks(kern, lds_bytes, 64 * WAVES) < 0) return -1;
+        if (kernel_allow_lds(kern, lds_bytes)) return -1;
         const long nblocks = (n_out + Lf - 1) / Lf, nslots = (nblocks + WAVES - 1) / WAVES;
         const unsigned grid = (unsigned)(nslots < ctx().num_cus ? nslots : ctx().num_cus);
         // round 6: 4 098 .. 8 193 taps (fft64_np = 3, 4) = a second launch with partitions 2 and 3 on the stream delayed by 4 096 samples, adding to y
         const int launches = NP == 2 && fft64_np > 2 ? 2 : 1;
+        int wrote = 0;
         for (int l = 0; l < launches; l++) {
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x,
-                               (const float2 *)d_fft64_tables.p + (size_t)l * F64_TABLE_ELEMS2, y, M, n, n_out, nblocks,
-                               (M > 1 && l == 0) ? (float *)hist[cur ^ 1].p + hist_pad : (float *)nullptr, 0, (long)l * F4K_N, l);
+            float *ho = l == 0 ? h_out() : nullptr;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WAVES), lds_bytes, ctx().stream, h_in(), x,
+                               (const float2 *)d_fft64_tables.p + (size_t)l * F64_TABLE_ELEMS2, y, M, n, n_out, nblocks, ho, 0, (long)l * F4K_N, l);
             LR_LAUNCH_CHECK();
+            wrote |= wrote_hist(ho);
         }
-        hist_in_kernel = true;
-        return 0;
+        return wrote;
     }
     template <int VV>
     int launch_fft64_v(const float *x, long n, float *y, long n_out)
@@ -435,18 +393,17 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         if (run < 4 * (PP - 1) + 4) run = 4 * (PP - 1) + 4;
         const long nruns = (nblocks + run - 1) / run, nslots = (nruns + POLS_WPB * RPW - 1) / (POLS_WPB * RPW);
         const unsigned grid = (unsigned)(nslots < ctx().num_cus ? nslots : ctx().num_cus);
-        float *ho = (M > 1 && part0 == 0) ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * POLS_WPB), lds_bytes, ctx().stream, (const float *)hist[cur].p + hist_pad, x, (const float2 *)d_fft_tables.p, y, M, n,
+        float *ho = part0 == 0 ? h_out() : nullptr;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * POLS_WPB), lds_bytes, ctx().stream, h_in(), x, (const float2 *)d_fft_tables.p, y, M, n,
                            n_out, nblocks, run, part0, part0 > 0 ? 1 : 0, ho);
-        if (ho) hist_in_kernel = true;
         LR_LAUNCH_CHECK();
-        return 0;
+        return wrote_hist(ho);
     }
     template <int SS>
     int launch_pols(const float *x, long n, float *y, long n_out)
     {
         const int nparts = (M + FFT_PART - 1) / FFT_PART;
-        hist_in_kernel = false;
+        int wrote = 0;
         // partitions per launch: up to 3 at twelve waves per CU (a delay line of two spectra in registers, 168 registers per lane).  Round 5: a ComplexFloat32 filter of
         // four partitions and more (1 537 taps up) takes FOUR per launch at eight waves per CU (three spectra, 256 registers): 4 096 taps in two launches instead
         // of three - same box, three alternations (profiles/r05_ab_pols_p4.txt): 1.4846 / 1.4822 / 1.4842 -> 1.1281 / 1.1296 / 1.1158 ms on 2^26 samples.
@@ -457,9 +414,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             int rc;
             if constexpr (SS == 2) rc = P == 4 ? launch_pols_p<SS, 4>(x, n, y, n_out, p0) : P == 3 ? launch_pols_p<SS, 3>(x, n, y, n_out, p0) : P == 2 ? launch_pols_p<SS, 2>(x, n, y, n_out, p0) : launch_pols_p<SS, 1>(x, n, y, n_out, p0);
             else rc = P == 3 ? launch_pols_p<SS, 3>(x, n, y, n_out, p0) : P == 2 ? launch_pols_p<SS, 2>(x, n, y, n_out, p0) : launch_pols_p<SS, 1>(x, n, y, n_out, p0);
-            if (rc) return rc;
+            if (rc < 0) return rc;
+            wrote |= rc;
         }
-        return 0;
+        return wrote;
     }
 
     int launch_fft(const float *x, long n, float *y, long n_out)
@@ -472,8 +430,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             case FirFftForm::Pass1024: break;
         }
         const size_t lds_bytes = (size_t)FFT_LDS_ELEMS * sizeof(float2) + (size_t)fir_knobs().fft_lds_pad;
-        const float *h = (const float *)hist[cur].p + hist_pad;
-        hist_in_kernel = false;
+        const float *h = h_in();
+        int wrote = 0;
         // one launch per partition of at most FFT_PART taps (a plain filter has one); partitions after the first accumulate
         const int nparts = (M + FFT_PART - 1) / FFT_PART;
         for (int part = 0; part < nparts; part++) {
@@ -483,9 +441,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             long nffts = S == 2 ? nblocks : (nblocks + 1) / 2;
             const float2 *tables = (const float2 *)d_fft_tables.p + (size_t)part * FFT_TABLE_ELEMS;
             auto go = [&](auto kern) -> int {
-                if (!fft_blocks_per_cu && prepare_kernel(kern, lds_bytes, &fft_blocks_per_cu, 64 * FFT_WPB)) return -1;
-                long slots = (long)ctx().num_cus * fft_blocks_per_cu;
-                long want = (nffts + FFT_WPB - 1) / FFT_WPB;
+                const long slots = chip_slots(kern, 64 * FFT_WPB, lds_bytes), want = (nffts + FFT_WPB - 1) / FFT_WPB;
+                if (slots < 0) return -1;
                 // one-shot order with 8 batches per workgroup once the launch exceeds the resident slots: 316 GS/s against 263-314
                 // (run-to-run spread) for the persistent stride on 2^28 samples, same box, alternating
                 // (only when the launch is many times the resident slots: a 2^26-sample chain's 1/5-rate audio filter, 1 873 workgroups
@@ -494,9 +451,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                 // now the faster order at every size - 2^26 samples 0.2155 against 0.2368 ms, 2^27 0.4199 / 0.4357, 2^28 0.8359 / 0.8412 and 0.8591 / 0.8646; the
                 // Float32 and complex-taps filters at 2^26 gain 9 % - a launch of 8-batch workgroups ends with a ragged last round that the one-block stride
                 // does not have.  The one-shot order stays as LRHIP_FFT_ROUNDS=8.
-                int rounds = fir_knobs().fft_rounds >= 0 ? fir_knobs().fft_rounds : 0;
-                if (want <= slots) rounds = 0;
-                unsigned grid = rounds > 0 ? (unsigned)((want + rounds - 1) / rounds) : (unsigned)(want < slots ? want : slots);
+                const int rounds = persistent_rounds(want, slots, fir_knobs().fft_rounds);
+                unsigned grid = persistent_grid(want, slots, rounds);
                 // input / output in HOST memory (host_execute's direct mode, chain.h): a short persistent grid, so that the reads of one block and the writes of
                 // another share the link instead of every wave loading, then every wave storing
                 if (host_io_grid() > 0 && rounds == 0 && grid > (unsigned)host_io_grid()) grid = (unsigned)host_io_grid();
@@ -517,8 +473,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                         grid = (unsigned)(n_full + k1 + k2 + k3);
                     }
                 }
-                const float2 *dp = pre_disc ? (const float2 *)disc_prev.p + disc_cur : nullptr;
-                float *ho = (!pre_disc && M > 1 && part == 0) ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+                const float2 *dp = pre_disc ? disc_in() : nullptr;
+                float *ho = (!pre_disc && part == 0) ? h_out() : nullptr;      // (pre_disc: the history is discriminator output, commit()'s kernel writes it)
 #ifdef LRHIP_FFT_TRACE
                 static unsigned long long *trace = nullptr;
                 static long trace_launches = 0;
@@ -556,14 +512,14 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                     }
                 }
 #endif
-                if (ho) hist_in_kernel = true;
-                return 0;
+                return wrote_hist(ho);
             };
             int rc = S == 2 ? go(fir_fft_kernel<2, 0>) : pre_disc ? go(fir_fft_kernel<1, 1>) : go(fir_fft_kernel<1, 0>);
-            if (rc) return rc;
+            if (rc < 0) return rc;
             LR_LAUNCH_CHECK();
+            wrote |= rc;
         }
-        return 0;
+        return wrote;
     }
 
     // decimations without a Toeplitz instantiation (and taps too long for its LDS table): LDS-staged one-output-per-thread kernel, first or second form (decim_lds2_ok)
@@ -581,8 +537,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         long span = (long)(OW - 1 + dsc) * D + M;
         size_t lds_bytes = v2 ? ((size_t)((M + 3) & ~3) + (size_t)2 * decim2_slots((int)span, (long)D)) * sizeof(float)
                               : ((size_t)(((taps_complex ? 2 : 1) * M + 3) & ~3) + (size_t)S * (span + (span >> 5) + 2)) * sizeof(float);
-        const float *h = (const float *)hist[cur].p + hist_pad;
-        float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+        const float *h = h_in();
+        float *ho = h_out();
         // (more: what the second form's kernels take behind `rounds`)
         auto go = [&](auto kern, auto... more) -> int {
             const long slots = chip_slots(kern, 256, lds_bytes);
@@ -590,15 +546,11 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             const int rounds = persistent_rounds(ntiles, slots, fir_knobs().decim_rounds);
             hipLaunchKernelGGL(kern, dim3(persistent_grid(ntiles, slots, rounds)), dim3(256), lds_bytes, ctx().stream, h, x, (const float *)d_taps.p, y, M, n, n_out, (long)index,
                                (long)D, OW, ntiles, rot ? rot_step : (uint64_t)0, rot ? count : (uint64_t)0, ho, post_unary, rounds, more...);
-            hist_in_kernel = ho != nullptr;
             return 0;
         };
         auto go2 = [&](auto kern) -> int {
-            float2 *dp = (float2 *)disc_prev.p;
-            if (go(kern, 1.0 / disc_gain, dsc ? (const float2 *)(dp + disc_cur) : (const float2 *)nullptr, dsc ? dp + (disc_cur ^ 1) : (float2 *)nullptr,
-                   rel_rot ? 0 : 1)) return -1;      // an exact chain keeps one fmaf chain per output (no tap split over the half-waves)
-            if (dsc) disc_cur ^= 1;
-            return 0;
+            return go(kern, 1.0 / disc_gain, dsc ? disc_in() : (const float2 *)nullptr, dsc ? disc_out() : (float2 *)nullptr,
+                      rel_rot ? 0 : 1);      // an exact chain keeps one fmaf chain per output (no tap split over the half-waves)
         };
         int rc;
         if (v2) {
@@ -621,7 +573,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                         : (rot ? set_error("rotator fusion needs complex input") : go(fir_decim_lds_kernel<1, false>));
         if (rc) return rc;
         LR_LAUNCH_CHECK();
-        return 0;
+        return wrote_hist(ho) | (dsc ? WROTE_DISC : 0);
     }
 
     template <int DD>
@@ -637,8 +589,8 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         pr.inv_gain = 1.0 / disc_gain;
         pr.taps_rev = (const float *)d_taps.p; pr.taps_complex = taps_complex;
         pr.dbg = ablation_bits("LRHIP_DECFFT_DBG");      // ablation knob (tools/ab_decfft.py): 0 unless the library was built with -DLRHIP_ABLATION
-        const float *h = (const float *)hist[cur].p + hist_pad;
-        float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+        const float *h = h_in();
+        float *ho = h_out();
         auto go = [&](auto kern) -> int {
             const long nquads = (pr.nblocks + 3) / 4, slots = chip_slots(kern, 256, lds_bytes);
             if (slots < 0) return -1;
@@ -648,24 +600,21 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             int rounds = fir_knobs().decfft_rounds > 0 ? fir_knobs().decfft_rounds : (nquads >= 16 * slots ? 4 : nquads >= 8 * slots ? 2 : 1);
             pr.rounds = rounds;
             const long wgs = (nquads + 4L * rounds - 1) / (4L * rounds);
-            float2 *dp = (float2 *)disc_prev.p;
             hipLaunchKernelGGL(kern, dim3((unsigned)wgs), dim3(256), lds_bytes, ctx().stream, h, x, (const float2 *)d_dec_tables.p, y, pr,
-                               post_disc ? (const float2 *)(dp + disc_cur) : nullptr, post_disc ? dp + (disc_cur ^ 1) : nullptr, ho);
-            hist_in_kernel = ho != nullptr;
+                               post_disc ? disc_in() : nullptr, post_disc ? disc_out() : nullptr, ho);
             return 0;
         };
         int rc = post_disc ? go(fir_decfft_kernel<DD, 1>) : go(fir_decfft_kernel<DD, 0>);
         if (rc) return rc;
         LR_LAUNCH_CHECK();
-        if (post_disc) disc_cur ^= 1;
-        return 0;
+        return wrote_hist(ho) | (post_disc ? WROTE_DISC : 0);
     }
 
     int launch_direct(const float *x, long n, float *y, long n_out)
     {
         if (rot) return set_error("internal: direct FIR kernel has no fused rotator");
         unsigned grid = grid_for((unsigned long)n_out, 256);
-        const float *h = (const float *)hist[cur].p + hist_pad, *t = (const float *)d_taps.p;
+        const float *h = h_in(), *t = (const float *)d_taps.p;
         if (S == 1)
             hipLaunchKernelGGL(fir_direct_kernel<0>, dim3(grid), dim3(256), 0, ctx().stream, h, x, t, y, M, n, n_out, (long)index, (long)D);
         else if (!taps_complex)
@@ -686,20 +635,18 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         if (slots < 0) return -1;
         FwrParams pr;
         memset(&pr, 0, sizeof(pr));
-        pr.hist = (const float *)hist[cur].p + hist_pad; pr.x = x; pr.n = n; pr.taps_rev = (const float *)d_taps.p; pr.y = y;
-        pr.hist_out = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+        pr.hist = h_in(); pr.x = x; pr.n = n; pr.taps_rev = (const float *)d_taps.p; pr.y = y;
+        pr.hist_out = h_out();
         pr.run = ONESHOT ? 1 : (ntiles + slots - 1) / slots;
         pr.dec = 1;
         hipLaunchKernelGGL(kern, dim3((unsigned)((ntiles + pr.run - 1) / pr.run)), dim3(256), lds_bytes, ctx().stream, pr);
         LR_LAUNCH_CHECK();
-        hist_in_kernel = pr.hist_out != nullptr;
-        return 0;
+        return wrote_hist(pr.hist_out);
     }
     // register-window kernel of kernels_firwin2.h (fir_win_cplx_ok, fir_win_pair_ok, fir_win_short_ok) and the recurrence fused behind its pair mode
     float iir_b0 = 1.f, iir_na1 = 0.f, iir_na1_lo = 0.f;
     int iir_warm = 1;
-    DeviceBuf d_iir_ptab, iir_state[2];
-    int iir_cur = 0;
+    DeviceBuf d_iir_ptab;
     // first-order recurrence behind the pair-mode filter: needs |a1|^(320 w) < 1e-12 for the in-launch warm-up (w waves of 64 lanes x 5 outputs)
     // The pole q (a double: p^D of the polyphase identity) is carried as a Float32 pair hi + lo: rounded to one Float32 its relative error of
     // 2^-24 moves the DC gain by 2^-24 q / (1 - q), which for a slow filter is far above the 1e-6 parity bar of the recurrence it replaces.
@@ -729,20 +676,19 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         if (slots < 0) return -1;
         FwcParams pr;
         memset(&pr, 0, sizeof(pr));
-        pr.hist = (const float *)hist[cur].p + hist_pad; pr.x = x; pr.n = n; pr.taps_rev = (const float *)(G::CTAPS ? d_ctaps4.p : d_taps.p); pr.y = y;
+        pr.hist = h_in(); pr.x = x; pr.n = n; pr.taps_rev = (const float *)(G::CTAPS ? d_ctaps4.p : d_taps.p); pr.y = y;
         pr.n_out = n_out; pr.first = (long)index;
-        pr.hist_out = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+        pr.hist_out = h_out();
         pr.ntiles = G::PAIR ? (n_out + 2L * G::TO - 1) / (2L * G::TO) : (n_out + G::TA - 1) / G::TA;
         pr.rot_step_fx = rot ? rot_step : 0; pr.rot_count0 = rot ? count : 0;
         if (G::DISC) {
-            float2 *dp = (float2 *)disc_prev.p;
-            pr.prev_in = dp + disc_cur; pr.prev_out = dp + (disc_cur ^ 1);
+            pr.prev_in = disc_in(); pr.prev_out = disc_out();
             pr.inv_gain = 1.0 / disc_gain;
         }
         unsigned grid;
         if (G::IIR) {
             pr.b0 = iir_b0; pr.na1 = iir_na1; pr.na1_lo = iir_na1_lo; pr.ptab = (const float *)d_iir_ptab.p; pr.warm_waves = iir_warm;
-            pr.state_in = (const float *)iir_state[iir_cur].p; pr.state_out = (float *)iir_state[iir_cur ^ 1].p;
+            pr.state_in = iir_in(); pr.state_out = iir_out();
             pr.fix_edge = pr.fix_prev = (const float2 *)d_iir_ptab.p;          // readable dummies (64 floats): the kernel loads unconditionally
             pr.fix_inv_gain = 1.0;
             if (fix_src && fix_src->fix_ready) {
@@ -764,10 +710,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         }
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, pr);
         LR_LAUNCH_CHECK();
-        hist_in_kernel = pr.hist_out != nullptr;
-        if (G::DISC) disc_cur ^= 1;
-        if (G::IIR) iir_cur ^= 1;
-        return 0;
+        return wrote_hist(pr.hist_out) | (G::DISC ? WROTE_DISC : 0) | (G::IIR ? WROTE_IIR : 0);
     }
     int launch_win_cplx(const float *x, long n, float *y, long n_out)
     {
@@ -776,14 +719,13 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     }
     int launch_short_real(const float *x, long n, float *y)
     {
-        const float *h = (const float *)hist[cur].p + hist_pad, *t = (const float *)d_taps.p;
-        float *ho = M > 1 ? (float *)hist[cur ^ 1].p + hist_pad : nullptr;
+        const float *h = h_in(), *t = (const float *)d_taps.p;
+        float *ho = h_out();
         const unsigned grid = grid_for((unsigned long)((n + 3) / 4), 256);
         if (M == 16) hipLaunchKernelGGL(fir_short_real_kernel<16>, dim3(grid), dim3(256), 0, ctx().stream, h, x, t, y, n, ho);
         else hipLaunchKernelGGL(fir_short_real_kernel<32>, dim3(grid), dim3(256), 0, ctx().stream, h, x, t, y, n, ho);
         LR_LAUNCH_CHECK();
-        hist_in_kernel = ho != nullptr;
-        return 0;
+        return wrote_hist(ho);
     }
 
     template <int SS>
@@ -803,11 +745,50 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
         }
     }
 
-    // filter n inputs (device), emit the retained outputs; advances history / index / count
+    // The one place where the carried state advances, behind a call's launches.  wrote: what they wrote into the next slots (WROTE_*).  The history is
+    // carried here where no launch did - a call that emits nothing launches no filter and still carries it; x is read for that alone - and exactly the
+    // slots that were written become current
+    int commit(long n, long n_out, int wrote, const float *x = nullptr)
+    {
+        if (pre_disc) {
+            // (the history is discriminator output: real taps, no pad, M >= 32 - plan_disc_fir)
+            unsigned grid = grid_for((unsigned long)(M > 1 ? M - 1 : 1), 256);
+            hipLaunchKernelGGL(fir_fft_pre_history_kernel, dim3(grid), dim3(256), 0, ctx().stream, h_in(), x, h_out(), M, n, 1.0 / disc_gain, disc_in(), disc_out());
+            LR_LAUNCH_CHECK();
+            wrote |= WROTE_HIST | WROTE_DISC;
+        } else if (!(wrote & WROTE_HIST) && M > 1) {
+            unsigned grid = grid_for((unsigned long)(M - 1) * S, 256);
+            if (S == 1)
+                hipLaunchKernelGGL(fir_history_kernel<1>, dim3(grid), dim3(256), 0, ctx().stream, h_in(), x, h_out(), M, n);
+            else
+                hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, h_in(), x, h_out(), M, n);
+            LR_LAUNCH_CHECK();
+        }
+        hist.flip();
+        if (wrote & WROTE_DISC) disc.flip();
+        if (wrote & WROTE_IIR) iir.flip();
+        index = index + (unsigned long)n_out * D - (unsigned long)n;
+        count += (uint64_t)n;
+        return 0;
+    }
+
+    // HilbertTransformBlock in one launch (hilbert_ok): 0, or -1 with the message set.  D = 1: the index stays 0
+    int hilbert(const float *x, long n, float *y2)
+    {
+        if (hilb_sparse < 0) {
+            hilb_sparse = (M == 65 || M == 129) ? 1 : 0;
+            for (int j = 0; j < M && hilb_sparse; j += 2)
+                if (taps_rev[(size_t)j] != 0.0f) hilb_sparse = 0;
+        }
+        const bool win = hilb_sparse && !fir_knobs().hilbert_mfma && index == 0;
+        const int wrote = !win ? launch_hilbert_mfma(x, n, y2) : M == 65 ? launch_hilbert_win<65>(x, n, y2) : launch_hilbert_win<129>(x, n, y2);
+        return wrote < 0 ? -1 : commit(n, n, wrote, x);
+    }
+
+    // filter n inputs (device), emit the retained outputs; commit() advances history / index / count
     long core(const float *x, long n, float *y, unsigned long cap)
     {
         if (n <= 0) return 0;
-        hist_in_kernel = false;
         fix_ready = false;
         long n_out = (unsigned long)n > index ? (long)((n - index + D - 1) / D) : 0;
         if ((unsigned long)n_out > cap) return set_error("fir: output capacity %lu < %ld", cap, n_out);
@@ -820,6 +801,7 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
             LR_LAUNCH_CHECK();
             fix_src->fix_ready = false;
         }
+        int wrote = 0;
         if (n_out > 0) {
             const FirForm f = form((uintptr_t)x % (raw_now ? (in_fmt == RX_FMT_S16LE ? 4u : 2u) : 4u * (unsigned)S) == 0);      // (aligned to the sample - raw records: the record - size?)
             int rc = -1;
@@ -837,32 +819,10 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
                 case FirForm::MfmaCc: rc = dispatch_mfma_cc(x, n, y, n_out); break;
                 case FirForm::MfmaPersistent: case FirForm::MfmaGeneric: rc = S == 1 ? dispatch_mfma<1>(f == FirForm::MfmaPersistent, x, n, y, n_out) : dispatch_mfma<2>(f == FirForm::MfmaPersistent, x, n, y, n_out); break;
             }
-            if (rc) return rc;
+            if (rc < 0) return rc;
+            wrote = rc;
         }
-        if (pre_disc) {
-            unsigned grid = grid_for((unsigned long)(M > 1 ? M - 1 : 1), 256);
-            float2 *dp = (float2 *)disc_prev.p;
-            hipLaunchKernelGGL(fir_fft_pre_history_kernel, dim3(grid), dim3(256), 0, ctx().stream, (const float *)hist[cur].p, x, (float *)hist[cur ^ 1].p, M, n,
-                               1.0 / disc_gain, (const float2 *)(dp + disc_cur), dp + (disc_cur ^ 1));
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-            disc_cur ^= 1;
-        } else if (hist_in_kernel) {
-            cur ^= 1;
-        } else if (M > 1) {
-            unsigned grid = grid_for((unsigned long)(M - 1) * S, 256);
-            const float *hi = (const float *)hist[cur].p + hist_pad;
-            float *ho = (float *)hist[cur ^ 1].p + hist_pad;
-            if (S == 1)
-                hipLaunchKernelGGL(fir_history_kernel<1>, dim3(grid), dim3(256), 0, ctx().stream, hi, x, ho, M, n);
-            else
-                hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, hi, x, ho, M, n);
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-        }
-        index = index + (unsigned long)n_out * D - (unsigned long)n;
-        count += (uint64_t)n;
-        return n_out;
+        return commit(n, n_out, wrote, x) ? -1 : n_out;
     }
 
     // does this chunk reach the persistent Tuner kernel, the one with a record instantiation?  (core()'s dispatch, the D = 5 / 128-tap shape)

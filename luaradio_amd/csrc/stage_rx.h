@@ -8,7 +8,6 @@ struct RxStage : lrhip_stage {
     std::unique_ptr<FirStage> A, B;       // state lives in the two stages, in their own formats: both forms can alternate chunk by chunk
     DeviceBuf mid;                        // two-launch form: the discriminator stream between them
     DeviceBuf d_ptab4;
-    int blocks_per_cu = 0, blocks_per_cu8 = 0;
     int in_fmt = RX_FMT_CF32;             // RX_FMT_* of the folded format stage
     // round 3: an IQFileSource format stage for unsigned 8-bit records directly in front of the receiver is folded into it (lrhip_chain_create): the single
     // launch reads the 2-byte records and converts them on the way into LDS (kernels_rx.h, U8); the stage itself (not owned) serves the fall-back form
@@ -108,7 +107,6 @@ struct RxStage : lrhip_stage {
         if ((unsigned long)n_out_b > cap) return set_error("fm-receiver: output capacity %lu < %ld", cap, n_out_b);
         const float *x = (const float *)in_dev;
         const size_t lds_bytes = (size_t)RX_LDS_FLOATS * sizeof(float);
-        int &bpc = u8 ? blocks_per_cu8 : blocks_per_cu;
         const int fmt_k = u8 ? in_fmt : RX_FMT_CF32;
         auto with_kernel = [&](auto fn) -> int {
             switch (fmt_k) {
@@ -118,34 +116,25 @@ struct RxStage : lrhip_stage {
                 default: return fn(rx_fused_kernel<RX_FMT_CF32>);
             }
         };
-        if (!bpc) {
-            const int rc0 = with_kernel([&](auto kern) -> int {
-                LR_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-                int nb = 0;
-                LR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds_bytes));
-                bpc = nb < 1 ? 1 : nb;
-                return 0;
-            });
-            if (rc0) return rc0;
-        }
+        const int bpc = with_kernel([&](auto kern) -> int { return kernel_slots(kern, 256, lds_bytes); });
+        if (bpc < 0) return -1;
         RxParams pr;
         memset(&pr, 0, sizeof(pr));
-        pr.hist = (const float *)A->hist[A->cur].p; pr.x = x; pr.n = n; pr.taps_pad = (const float *)A->d_atab.p;
+        pr.hist = A->h_in(); pr.x = x; pr.n = n; pr.taps_pad = (const float *)A->d_atab.p;
         pr.n_out_a = n_out_a; pr.first_a = (long)A->index;
         // alignment of the staged window (16-byte loads of ComplexFloat32 pairs, 4-byte loads of record pairs): slack of 0 or 1 sample
         const long v = (long)((uintptr_t)x / (u8 ? (in_fmt == RX_FMT_S16LE ? 4 : 2) : 8)) + (long)A->index - (RX_M - 1);
         pr.e = (int)(((v % 2) + 2) % 2);
         pr.ntiles = (n_out_a + RX_TILE - 1) / RX_TILE;
         pr.rot_step_fx = A->rot_step; pr.rot_count0 = A->count;
-        float2 *dp = (float2 *)A->disc_prev.p;
-        pr.prev_in = dp + A->disc_cur; pr.prev_out = dp + (A->disc_cur ^ 1);
+        pr.prev_in = A->disc_in(); pr.prev_out = A->disc_out();
         pr.inv_gain = 1.0 / A->disc_gain;
-        pr.hist_out = (float *)A->hist[A->cur ^ 1].p;
+        pr.hist_out = A->h_out();
         pr.g_pad = (const float *)B->d_atab.p;
-        pr.thist_in = (const float *)B->hist[B->cur].p; pr.thist_out = (float *)B->hist[B->cur ^ 1].p;
+        pr.thist_in = B->h_in(); pr.thist_out = B->h_out();
         pr.first_b = (long)B->index; pr.n_out_b = n_out_b; pr.y = (float *)out_dev;
         pr.b0 = B->iir_b0; pr.na1 = B->iir_na1; pr.na1_lo = B->iir_na1_lo; pr.ptab4 = (const float *)d_ptab4.p;
-        pr.state_in = (const float *)B->iir_state[B->iir_cur].p; pr.state_out = (float *)B->iir_state[B->iir_cur ^ 1].p;
+        pr.state_in = B->iir_in(); pr.state_out = B->iir_out();
         // one round of workgroups: as many as fit the chip at once; a run costs one extra tile, so short chunks take fewer, longer runs
         long wgs = (long)ctx().num_cus * bpc;
         static const long env_wgs = getenv("LRHIP_RX_WGS_PER_CU") ? atol(getenv("LRHIP_RX_WGS_PER_CU")) : 0;       // A/B knob, read once
@@ -193,14 +182,8 @@ struct RxStage : lrhip_stage {
             }
         }
 #endif
-        // what FirStage::core() does for each of the two stages
-        A->hist_in_kernel = true; A->fix_ready = false;
-        A->cur ^= 1; A->disc_cur ^= 1;
-        A->index = A->index + (unsigned long)n_out_a * RX_D - (unsigned long)n;
-        A->count += (uint64_t)n;
-        B->cur ^= 1; B->iir_cur ^= 1;
-        B->index = B->index + (unsigned long)n_out_b * RX_D - (unsigned long)n_out_a;
-        B->count += (uint64_t)n_out_a;
+        // the one launch wrote both stages' next slots: no history kernel runs
+        if (A->commit(n, n_out_a, FirStage::WROTE_HIST | FirStage::WROTE_DISC) || B->commit(n_out_a, n_out_b, FirStage::WROTE_HIST | FirStage::WROTE_IIR)) return -1;
         last_form = u8 ? 3 : 1;
         return n_out_b;
     }

@@ -6,7 +6,8 @@ Why: a Hamming-window lowpass is exactly symmetric in Float32, h[k] == h[M-1-k],
 Toeplitz table built mirrored - produces the same terms in the same order and passes even a bit-exact comparison.  With these taps it does not.
 
 Stream lengths: with T the outputs of one tile of the form (tests/test_gpu_bounds.py TILES and the lines it cites, restated by mfma_tile() /
-lds_tile() below) a case runs 3 T D + T D / 2 + 7 input samples, once whole and once as calls of 1, 2 T D + 3 and the rest."""
+lds_tile() below) a case runs 3 T D + T D / 2 + 7 input samples, once whole and once as calls of 1, 2 T D + 3 and the rest; a case that decimates
+also as calls of 1, 1, 2 T D + 3 and the rest, whose second call emits nothing (idle_call_lengths)."""
 import collections
 import zlib
 
@@ -38,20 +39,20 @@ def skewed_lowpass(M, cutoff):
 
 # ------------------------------------------------------------------------------------------------------------------------ tiles
 def mfma_tile(cplx, D):
-    """kernels_fir.h:184 tile_out = nw * nacc * (16 / S) * 16 with the accumulators per wave of stage_fir.h:806-815 (dispatch_mfma)"""
+    """kernels_fir.h:184 tile_out = nw * nacc * (16 / S) * 16 with the accumulators per wave of stage_fir.h dispatch_mfma"""
     nacc = {1: 8, 2: 4, 3: 2, 4: 2, 5: 2}.get(D, 1)
     return 4 * nacc * (8 if cplx else 16) * 16
 
 
 def lds_tile(M, D, second_form, disc=0):
-    """stage_fir.h:580 OW = (span_max - M) / D + 1 - dsc, at most 256 - 4 dsc; span_max = DECIM2_SPAN_MAX 6128 / DECIM_SPAN_MAX 6144"""
+    """stage_fir.h launch_decim_lds: OW = (span_max - M) / D + 1 - dsc, at most 256 - 4 dsc; span_max = DECIM2_SPAN_MAX 6128 / DECIM_SPAN_MAX 6144"""
     return min(256 - 4 * disc, ((6128 if second_form else 6144) - M) // D + 1 - disc)
 
 
-DECFFT_TILE = 3584      # stage_fir.h:662 workgroups of 4 waves x one quad of 4 blocks, kernels_firdecfft.h:55 DF_LO = 224 outputs per block
-PAIR_TILE = 2560        # stage_fir.h:748 ntiles over 2 * G::TO, TO = 256 * 5
-PASS1024R_TILE = 1792   # stage_fir.h:482 Lf = 1024 - 128 = 896, two blocks of a Float32 stream per transform
-D1_TILE = 4096          # stage_fir.h:807 launch_mfma<2, 1, 8>
+DECFFT_TILE = 3584      # stage_fir.h launch_decfft_d: workgroups of 4 waves x one quad of 4 blocks, kernels_firdecfft.h:55 DF_LO = 224 outputs per block
+PAIR_TILE = 2560        # stage_fir.h launch_win_cplx_m: ntiles over 2 * G::TO, TO = 256 * 5
+PASS1024R_TILE = 1792   # stage_fir.h launch_fft: Lf = 1024 - 128 = 896, two blocks of a Float32 stream per transform
+D1_TILE = 4096          # stage_fir.h dispatch_mfma: launch_mfma<2, 1, 8>
 
 
 def stream_len(T, D):
@@ -62,6 +63,19 @@ def call_lengths(n, T, D):
     """the chunked run of a case: calls of 1, 2 T D + 3 and the rest"""
     a = 2 * T * D + 3
     return [1, a, n - 1 - a]
+
+
+def idle_call_lengths(n, T, D):
+    """a second chunking for D >= 2: calls of 1, 1, 2 T D + 3 and the rest.  The first call leaves the decimation index at D - 1, so the second one
+    emits nothing: no filter launch, the history is carried by its own kernel, and no discriminator or recurrence state may move"""
+    assert D >= 2
+    a = 2 * T * D + 3
+    return [1, 1, a, n - 2 - a]
+
+
+def chunkings(case):
+    """the chunked runs of a case: call_lengths, and idle_call_lengths where the case decimates (at D = 1 every call emits)"""
+    return [call_lengths(case.n, case.T, case.D)] + ([idle_call_lengths(case.n, case.T, case.D)] if case.D >= 2 else [])
 
 
 # ------------------------------------------------------------------------------------------------------------------------ cases

@@ -95,3 +95,8 @@ def test_stream_lengths_and_calls():
         assert c.n == 3 * c.T * c.D + c.T * c.D // 2 + 7, c.name
         calls = A.call_lengths(c.n, c.T, c.D)
         assert calls[0] == 1 and calls[1] == 2 * c.T * c.D + 3 and sum(calls) == c.n and min(calls) > 0, c.name
+        assert A.chunkings(c)[0] == calls and len(A.chunkings(c)) == (2 if c.D >= 2 else 1), c.name
+        if c.D >= 2:
+            # the first call of 1 leaves the carried index at D - 1; a call of m samples emits only when m exceeds it
+            idle = A.idle_call_lengths(c.n, c.T, c.D)
+            assert idle[:3] == [1, 1, 2 * c.T * c.D + 3] and len(idle) == 4 and sum(idle) == c.n and min(idle) > 0 and idle[1] <= c.D - 1, c.name

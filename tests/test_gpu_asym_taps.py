@@ -2,7 +2,8 @@
 references from oracle stages; tests/test_asym_taps_cpu.py holds the table to its purpose).  A Hamming lowpass is h[k] == h[M-1-k] to the bit, so a kernel
 that walks its taps backwards or a mirrored polyphase / Toeplitz table passes every test that uses one; with these taps it is off by 2 % of the output and more.
 
-Each case is three tiles and a half plus 7 samples, run whole and as calls of 1, 2 T D + 3 and the rest, at the bar of the existing test of the same form,
+Each case is three tiles and a half plus 7 samples, run whole and as calls of 1, 2 T D + 3 and the rest (the FIR stage, tuner, discriminator-epilogue and
+polyphase-tail rows that decimate also as calls of 1, 1, 2 T D + 3 and the rest: the second call emits nothing), at the bar of the existing test of the same form,
 with that test's launch count (or, for one FIR stage, the row "asym: ..." of tools/host_fir_form_check.hip that pins the FirForm of the shape)."""
 import os
 
@@ -62,6 +63,16 @@ def in_calls(obj, x, lengths):
     return np.concatenate(parts)
 
 
+def chunked_runs(obj, x, case):
+    """the case's chunked runs (A.chunkings: calls of 1, 2 T D + 3 and the rest; where it decimates also 1, 1, 2 T D + 3 and the rest, whose second
+    call emits nothing), each from a reset state"""
+    out = []
+    for calls in A.chunkings(case):
+        obj.reset()
+        out.append(in_calls(obj, x, calls))
+    return out
+
+
 def at_cuts(obj, x, cuts):
     ends = list(cuts) + [len(x)]
     return in_calls(obj, x, [b - a for a, b in zip([0] + ends[:-1], ends)])
@@ -100,17 +111,16 @@ def test_fir_stage(case):
     x, want = A.case_input(case), ref(case)
     blk = make(lr.FIRFilterBlock, [case.taps[0], case.p["use_fft"]], tp(case), 2.0, decimation=case.D)
     whole = blk.process(x)
-    blk.reset()
-    got = in_calls(blk, x, A.call_lengths(case.n, case.T, case.D))
-    assert len(whole) == len(got) == len(want) == (case.n + case.D - 1) // case.D
-    if case.bar == A.BITS:
-        assert np.array_equal(whole, want), float(np.max(np.abs(whole - want)))
-        assert np.array_equal(got, want), float(np.max(np.abs(got - want)))
-    else:
-        e1, e2, e3 = G.max_abs_err(whole, want), G.max_abs_err(got, want), G.max_abs_err(got, whole)
-        _note("DecFft against f64", case.name, max(e1, e2), case.bar)
-        _note("DecFft chunked against whole", case.name, e3, 5e-7)
-        assert e1 < case.bar and e2 < case.bar and e3 < 5e-7
+    for got in chunked_runs(blk, x, case):
+        assert len(whole) == len(got) == len(want) == (case.n + case.D - 1) // case.D
+        if case.bar == A.BITS:
+            assert np.array_equal(whole, want), float(np.max(np.abs(whole - want)))
+            assert np.array_equal(got, want), float(np.max(np.abs(got - want)))
+        else:
+            e1, e2, e3 = G.max_abs_err(whole, want), G.max_abs_err(got, want), G.max_abs_err(got, whole)
+            _note("DecFft against f64", case.name, max(e1, e2), case.bar)
+            _note("DecFft chunked against whole", case.name, e3, 5e-7)
+            assert e1 < case.bar and e2 < case.bar and e3 < 5e-7
 
 
 # ===================================================================================================== B. fused chains
@@ -138,16 +148,15 @@ def test_tuner(case):
     chain = lr.Chain(build(_tuner_specs(case), types.ComplexFloat32, rate))
     whole = chain.process(x)
     assert chain.last_launches <= 2          # one fused kernel + history carry
-    chain.reset()
-    got = in_calls(chain, x, A.call_lengths(case.n, case.T, case.D))
-    assert len(got) == len(whole) == len(want)
-    assert np.array_equal(got, whole)
-    if case.p["toeplitz"]:
-        apart, _ = one_by_one(build(_tuner_specs(case), types.ComplexFloat32, rate), x)
-        assert np.array_equal(got, apart)
-    err = G.max_abs_err(got, want)
-    _note("tuner against the oracle", case.name, err, case.bar)
-    assert err < case.bar
+    apart = one_by_one(build(_tuner_specs(case), types.ComplexFloat32, rate), x)[0] if case.p["toeplitz"] else None
+    for got in chunked_runs(chain, x, case):
+        assert len(got) == len(whole) == len(want)
+        assert np.array_equal(got, whole)
+        if case.p["toeplitz"]:
+            assert np.array_equal(got, apart)
+        err = G.max_abs_err(got, want)
+        _note("tuner against the oracle", case.name, err, case.bar)
+        assert err < case.bar
 
 
 DISCS = [c for c in A.chain_cases() if c.group == "disc"]
@@ -170,8 +179,7 @@ def test_discriminator_epilogue(case, monkeypatch):
             assert chain.last_launches == p["launches"]
     else:
         assert chain.last_launches <= p["max_launches"]              # fused kernel + wave-boundary fix-up
-    chain.reset()
-    got = in_calls(chain, x, A.call_lengths(case.n, case.T, case.D))
+    gots = chunked_runs(chain, x, case)
     if case.name == "disc-lds2-d50":
         # the tuner as ONE fused chain (what TunerBlock runs), then the discriminator block
         tun = lr.Chain(build(_tuner_specs(case), types.ComplexFloat32, rate))
@@ -179,6 +187,12 @@ def test_discriminator_epilogue(case, monkeypatch):
         want = make(lr.FrequencyDiscriminatorBlock, [A.GAIN], types.ComplexFloat32, rate / case.D).process(o)
     else:
         want, o = one_by_one(build(_tuner_specs(case, True), types.ComplexFloat32, rate), x)
+    for got in gots:
+        _compare_discriminator_epilogue(case, whole, got, want, o)
+
+
+def _compare_discriminator_epilogue(case, whole, got, want, o):
+    """one chunked run `got` of test_discriminator_epilogue against the unfused device blocks (`want`, their filter outputs `o`) and the oracle"""
     assert len(got) == len(whole) == len(want) == (case.n + case.D - 1) // case.D
     if case.bar == A.BITS:
         assert np.array_equal(whole, want) and np.array_equal(got, want)
@@ -254,13 +268,12 @@ def test_polyphase_tail(case):
     whole = chain.process(x)
     lo, hi = case.p["launches_range"]
     assert lo <= chain.last_launches <= hi, chain.last_launches
-    chain.reset()
-    got = in_calls(chain, x, A.call_lengths(case.n, case.T, case.D))
-    assert len(got) == len(whole) == len(want)
-    e = max(G.max_abs_err(whole, want), G.max_abs_err(got, want))
-    _note("polyphase tail against the oracle", case.name, e, case.bar)
-    _note("polyphase tail chunked against whole", case.name, G.max_abs_err(got, whole), 5e-7)
-    assert e < case.bar and G.max_abs_err(got, whole) < 5e-7
+    for got in chunked_runs(chain, x, case):
+        assert len(got) == len(whole) == len(want)
+        e = max(G.max_abs_err(whole, want), G.max_abs_err(got, want))
+        _note("polyphase tail against the oracle", case.name, e, case.bar)
+        _note("polyphase tail chunked against whole", case.name, G.max_abs_err(got, whole), 5e-7)
+        assert e < case.bar and G.max_abs_err(got, whole) < 5e-7
 
 
 RXS = [c for c in A.chain_cases() if c.group == "rx"]

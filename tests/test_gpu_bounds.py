@@ -52,20 +52,20 @@ TILES = {
     "disc4": (1024, "stage_elem.h:87 grid_for(n / 4 + 1, 256): four samples per thread"),
     "fmod": (4096, "kernels_elem.h:718 FMOD_TILE = 256 * FMOD_LC = 4096"),
     "hilbwin": (4096, "kernels_firwin.h:39 FWR_TILE = 4096"),
-    "mfma1x4": (4096, "stage_fir.h:292 FirMfmaGeom<1, 1>::tile_out(4) = 4 waves * 4 * 16 * 16"),
+    "mfma1x4": (4096, "stage_fir.h launch_hilbert_mfma: FirMfmaGeom<1, 1>::tile_out(4) = 4 waves * 4 * 16 * 16"),
     "fmt": (1024, "stage_elem2.h:66 items = ns / 4 scalars per thread, 256 threads"),
     "pack": (256, "stage_elem2.h:41 grid_for(ns, 256): one scalar per thread"),
     # FIR forms (stage_fir.h, kernels_fir.h:184 tile_out = nw * nacc * (16 / S) * 16)
-    "decfft": (3584, "stage_fir.h:662 wgs of 4 waves x rounds (1) quads of 4 blocks, kernels_firdecfft.h:55 DF_LO = 224 outputs per block"),
-    "winshort": (1280, "kernels_firwin2.h:41 TO = 256 * R, R = 5 (stage_fir.h:845 FwcGeom<1, 5, M, 0>), TA = TO"),
-    "shortreal": (1024, "stage_fir.h:795 grid_for((n + 3) / 4, 256): four outputs per thread"),
-    "winpair": (2560, "stage_fir.h:748 ntiles over 2 * G::TO, TO = 256 * 5"),
-    "decimlds50": (121, "stage_fir.h:580 OW = (span_max - M) / D + 1 = (6144 or 6128 - 128) / 50 + 1"),
-    "direct": (256, "stage_fir.h:679 grid_for(n_out, 256)"),
-    "mfmacc": (4096, "stage_fir.h:345 launch_mfma_cc<2, 4>: FirMfmaGeom<1, 2>::tile_out(4)"),
-    "mfma2d1": (4096, "stage_fir.h:807 launch_mfma<2, 1, 8>: tile_out(8) = 4 * 8 * 8 * 16"),
-    "mfma1d1": (8192, "stage_fir.h:807 launch_mfma<1, 1, 8>: tile_out(8) = 4 * 8 * 16 * 16"),
-    "mfma2d5": (1024, "stage_fir.h:811 launch_mfma<2, 5, 2>: tile_out(2) = 4 * 2 * 8 * 16"),
+    "decfft": (3584, "stage_fir.h launch_decfft_d: wgs of 4 waves x rounds (1) quads of 4 blocks, kernels_firdecfft.h:55 DF_LO = 224 outputs per block"),
+    "winshort": (1280, "kernels_firwin2.h:41 TO = 256 * R, R = 5 (stage_fir.h core: launch_win_cplx_m<M, 0, 1, true> = FwcGeom<1, 5, M, 0>), TA = TO"),
+    "shortreal": (1024, "stage_fir.h launch_short_real: grid_for((n + 3) / 4, 256): four outputs per thread"),
+    "winpair": (2560, "stage_fir.h launch_win_cplx_m: ntiles over 2 * G::TO, TO = 256 * 5"),
+    "decimlds50": (121, "stage_fir.h launch_decim_lds: OW = (span_max - M) / D + 1 =(6144 or 6128 - 128) / 50 + 1"),
+    "direct": (256, "stage_fir.h launch_direct: grid_for(n_out, 256)"),
+    "mfmacc": (4096, "stage_fir.h dispatch_mfma_cc: launch_mfma_cc<2, 4>: FirMfmaGeom<1, 2>::tile_out(4)"),
+    "mfma2d1": (4096, "stage_fir.h dispatch_mfma: launch_mfma<2, 1, 8>: tile_out(8) = 4 * 8 * 8 * 16"),
+    "mfma1d1": (8192, "stage_fir.h dispatch_mfma: launch_mfma<1, 1, 8>: tile_out(8) = 4 * 8 * 16 * 16"),
+    "mfma2d5": (1024, "stage_fir.h dispatch_mfma: launch_mfma<2, 5, 2>: tile_out(2) = 4 * 2 * 8 * 16"),
     "iir": (4096, "kernels_iir.h:24 IIR_TILE = 256 * IIR_LC"),
     "agc": (2048, "kernels_agc.h:22 AGC_TILE = 256 * AGC_LC"),
 }
@@ -1042,13 +1042,13 @@ def test_shaped_modulator(kind, bits, period, down, exact):
 # one (host path, the same call lengths); the bar is bit equality where the chain's parity test asserts it and its tolerance otherwise.
 FS = 1102500.0
 TILES.update({
-    "cascade": (3328, "chain_plan.h:72 three 256-tap filters merge into 766 taps: the 4096-point kernel, 4096 - 768 outputs per block (stage_fir.h:357)"),
+    "cascade": (3328, "chain_plan.h:72 three 256-tap filters merge into 766 taps: the 4096-point kernel, 4096 - 768 outputs per block (stage_fir.h launch_fft4k_ng: Lf)"),
     "resample": (1024, "stage_resample.h:71 ntiles = ceil(n / tq) input samples per tile, tq <= 1024"),
     "rx": (25600, "kernels_rx.h:88 RX_BATCH = 5 120 discriminator samples per batch = 25 600 input samples at decimation 5"),
-    "tuner5": (5120, "stage_fir.h:811 launch_mfma<2, 5, 2>: 1024 outputs per tile at decimation 5"),
-    "tuner50": (6050, "stage_fir.h:580 OW = 121 outputs per tile at decimation 50"),
-    "tail": (12800, "stage_fir.h:748 pair mode: 2 * 1280 outputs per tile at decimation 5"),
-    "pass1024r": (1792, "stage_fir.h:482 Lf = 1024 - 128 = 896, two blocks of a Float32 stream per transform"),
+    "tuner5": (5120, "stage_fir.h dispatch_mfma: launch_mfma<2, 5, 2>: 1024 outputs per tile at decimation 5"),
+    "tuner50": (6050, "stage_fir.h launch_decim_lds: OW = 121 outputs per tile at decimation 50"),
+    "tail": (12800, "stage_fir.h launch_win_cplx_m: pair mode: 2 * 1280 outputs per tile at decimation 5"),
+    "pass1024r": (1792, "stage_fir.h launch_fft: Lf = 1024 - 128 = 896, two blocks of a Float32 stream per transform"),
 })
 
 

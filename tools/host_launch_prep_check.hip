@@ -9,7 +9,7 @@ using namespace lrhip;
 // stage_fir.h (persistent Toeplitz, both lambdas of launch_decim_lds): the gate, then the grid
 static int gate_a(long ntiles, long slots, int knob) { const int rounds = ntiles > slots && knob > 0 ? knob : 0; return rounds; }
 static unsigned grid_a(long ntiles, long slots, int rounds) { unsigned grid = rounds > 0 ? (unsigned)((ntiles + rounds - 1) / rounds) : (unsigned)(ntiles < slots ? ntiles : slots); return grid; }
-// stage_spectrum.h (LRHIP_SPEC_ROUNDS, -1 = unset); stage_fir.h launch_fft (LRHIP_FFT_ROUNDS) still spells it so
+// stage_spectrum.h (LRHIP_SPEC_ROUNDS, -1 = unset); stage_fir.h launch_fft (LRHIP_FFT_ROUNDS) spelled it so as well
 static int gate_b(long want, long slots, int knob)
 {
     int rounds = knob >= 0 ? knob : 0;
