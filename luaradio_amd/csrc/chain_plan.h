@@ -278,7 +278,7 @@ static int plan_phasecorr_real(Plan &p, unsigned i)
     f->real_out = true;
     f->in_size = 8; f->out_size = 4;
     if (f->reset()) return -1;
-    LR_HIP(hipMemcpyAsync(f->state.p, (const PcState *)pc->state.p + pc->cur, sizeof(PcState), hipMemcpyDeviceToDevice, ctx().stream));
+    LR_HIP(hipMemcpyAsync((PcState *)f->state.in(), pc->state.in(), sizeof(PcState), hipMemcpyDeviceToDevice, ctx().stream));
     LR_HIP(hipMemcpyAsync(f->ring.p, pc->ring.p, (size_t)pc->p.N * sizeof(unsigned long long), hipMemcpyDeviceToDevice, ctx().stream));
     f->off = pc->off;
     p.add(std::move(f));
@@ -375,7 +375,7 @@ static int digital_fuse_tail(std::vector<lrhip_chain::Op> &ops)
         // carried state: the clocksampler's, plus the decoder's previous input bit
         DgState *fs = (DgState *)f->st.in();                 // what the fused stage's first call reads
         LR_HIP(hipMemcpyAsync(fs, cs->st.in(), sizeof(DgState), hipMemcpyDeviceToDevice, ctx().stream));
-        if (dd) LR_HIP(hipMemcpyAsync(&fs->bit, (const uint8_t *)dd->state.p + dd->cur, 1, hipMemcpyDeviceToDevice, ctx().stream));
+        if (dd) LR_HIP(hipMemcpyAsync(&fs->bit, dd->state.in(), 1, hipMemcpyDeviceToDevice, ctx().stream));
         if (dd) LR_HIP(hipMemsetAsync((char *)&fs->bit + 1, 0, sizeof(int) - 1, ctx().stream));
         ops.erase(ops.begin() + (long)k + 1, ops.begin() + (long)k + (dd ? 3 : 2));
         ops[k] = lrhip_chain::Op(std::move(f));

@@ -55,6 +55,7 @@ static int g_launches = 0;   // kernels enqueued since the counter was last clea
     } while (0)
 
 #include "stage.h"
+#include "stage_carry.h"
 #include "op_string.h"
 #include "stage_counted.h"
 #include "stage_fir.h"

@@ -9,8 +9,8 @@
 struct ArbResampleStage : lrhip_stage {
     int S = 2, P = 0, log2p = 0, T = 0;
     uint64_t step = arbplan::ONE;
-    DeviceBuf d_tab, hist[2];         // d_tab: {G[p][k], D[p][k]} pairs at a row stride of T + 1 pairs, as the kernel keeps them in LDS
-    int cur = 0;
+    TwoSlots hist;                    // the T - 1 input samples in front of the next call
+    DeviceBuf d_tab;                  // d_tab: {G[p][k], D[p][k]} pairs at a row stride of T + 1 pairs, as the kernel keeps them in LDS
     uint64_t Q0 = 0, m0 = 0;
     const char *kind() const override { return "arbresampler"; }
     unsigned long max_output(unsigned long n) const override { return (unsigned long)arbplan::max_output(n, step); }
@@ -24,9 +24,8 @@ struct ArbResampleStage : lrhip_stage {
     }
     int reset() override
     {
-        cur = 0; Q0 = 0; m0 = 0;
-        const size_t hb = (size_t)(T - 1) * S * sizeof(float);
-        return (zero_fill(hist[0], hb) || zero_fill(hist[1], hb)) ? -1 : 0;
+        Q0 = 0; m0 = 0;
+        return hist.reset((size_t)(T - 1) * S * sizeof(float));
     }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
     {
@@ -53,15 +52,15 @@ struct ArbResampleStage : lrhip_stage {
             const long ntiles = (n_out + ARB_TILE - 1) / ARB_TILE, slots = chip_slots(kern, ARB_NT, lds_bytes);
             if (slots < 0) return -1;
             const unsigned grid = persistent_grid(ntiles, slots, 0);           // a workgroup stages the tables once and strides through the tiles
-            hipLaunchKernelGGL(kern, dim3(grid ? grid : 1), dim3(ARB_NT), lds_bytes, ctx().stream, (const float *)hist[cur].p, (const float *)in_dev,
+            hipLaunchKernelGGL(kern, dim3(grid ? grid : 1), dim3(ARB_NT), lds_bytes, ctx().stream, hist.in<float>(), (const float *)in_dev,
                                (const float2 *)d_tab.p, (float *)out_dev, T, log2p, step, (long)n, n_out, m0, Q0, arb_span_cap(step, T),
-                               (int)(((uintptr_t)out_dev & 7) == 0), (float *)hist[cur ^ 1].p);
+                               (int)(((uintptr_t)out_dev & 7) == 0), hist.out<float>());
             return 0;
         };
         const int rc = S == 2 ? go(arb_resample_kernel<2>) : go(arb_resample_kernel<1>);
         if (rc) return rc;
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();
         Q0 += n;
         m0 = c.lo;
         return n_out;

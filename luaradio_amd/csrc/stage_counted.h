@@ -1,51 +1,9 @@
 // stage_counted.h - the host pieces shared by the stages whose output count depends on the data (the sampler and clocksampler of stage_digital.h,
-// the preamble sampler, Manchester decoder and Varicode decoder of stage_preamble.h, the five framers of stage_framers.h): the state and the bytes carried between
-// calls, the one count read-back per call, the carve-up of a call's scratch, and the constructor of a stage without parameters.
-// (part of liblrhip.so; included by lrhip.hip after stage.h, one translation unit.  Plain host code: tools/host_carve_check.hip checks the
+// the preamble sampler, Manchester decoder and Varicode decoder of stage_preamble.h, the five framers of stage_framers.h): the carve-up of a call's
+// scratch and the constructor of a stage without parameters.  (What they carry between calls, and their one count read-back per call: stage_carry.h.)
+// (part of liblrhip.so; included by lrhip.hip after stage_carry.h, one translation unit.  Plain host code: tools/host_carve_check.hip checks the
 // scratch layouts on the CPU)
 #pragma once
-
-// State S, and BYTES carried bytes, each in two device slots that alternate: a call reads in() / ci(), its kernels write out() / co(), and
-// flip() makes what it wrote the next call's input.
-template <class S, int BYTES = 0> struct Carried {
-    DeviceBuf state, bytes;
-    PinnedBuf host;
-    int cur = 0;
-    // both slots = v, the carried bytes zero
-    int reset(const S &v)
-    {
-        cur = 0;
-        const S s[2] = {v, v};
-        if (upload(state, s, sizeof(s)) || host.reserve(sizeof(S))) return -1;
-        return BYTES ? zero_fill(bytes, 2 * (size_t)BYTES) : 0;
-    }
-    int reset() { S zero; memset(&zero, 0, sizeof(zero)); return reset(zero); }
-    const S *in() const { return (const S *)state.p + cur; }
-    S *out() { return (S *)state.p + (cur ^ 1); }
-    const uint8_t *ci() const { return (const uint8_t *)bytes.p + (size_t)cur * BYTES; }
-    uint8_t *co() { return (uint8_t *)bytes.p + (size_t)(cur ^ 1) * BYTES; }
-    void flip() { cur ^= 1; }
-    // The data-dependent count: the one small read-back of a stage, behind its last launch and flip().  Copies the state the call has just
-    // written into `got` and waits for the stream.
-    int fetch(S &got)
-    {
-        LR_HIP(hipMemcpyAsync(host.p, in(), sizeof(S), hipMemcpyDeviceToHost, ctx().stream));
-        LR_HIP(hipStreamSynchronize(ctx().stream));
-        got = *(const S *)host.p;
-        return 0;
-    }
-};
-
-// The same pair of alternating slots for a stage that sizes and fills them itself (FirStage's history, discriminator sample and recurrence
-// state): in() is what a call reads, out() what its kernels write, flip() makes that the next call's input.
-struct TwoSlots {
-    DeviceBuf slot[2];
-    int cur = 0;
-    int reset(size_t bytes) { cur = 0; return (zero_fill(slot[0], bytes) || zero_fill(slot[1], bytes)) ? -1 : 0; }
-    void *in() const { return slot[cur].p; }
-    void *out() const { return slot[cur ^ 1].p; }
-    void flip() { cur ^= 1; }
-};
 
 // ---- a call's scratch, carved into typed regions in the order they are taken, each aligned to its element type
 template <class T> struct Region {

@@ -182,20 +182,18 @@ struct SlicerStage : lrhip_stage {
 // =====================================================================================================
 struct DiffDecStage : lrhip_stage {
     int invert = 0;
-    DeviceBuf state;                         // two bytes, ping-pong: the last input byte of the previous call
-    int cur = 0;
+    Carried<uint8_t> state;                  // the last input byte of the previous call
     const char *kind() const override { return "differentialdecoder"; }
     long memory() const override { return 1; }
-    int reset() override { cur = 0; return zero_fill(state, 2); }
+    int reset() override { return state.reset(); }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
         if (n > cap) return set_error("differentialdecoder: output capacity %lu < %lu", cap, n);
         if (!n) return 0;
-        const uint8_t *s = (const uint8_t *)state.p;
         hipLaunchKernelGGL(diffdec_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const uint8_t *)in_dev, (uint8_t *)out_dev, n, invert,
-                           s + cur, (uint8_t *)state.p + (cur ^ 1));
+                           state.in(), state.out());
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        state.flip();
         return (long)n;
     }
 };

@@ -72,38 +72,36 @@ struct DownsamplerStage : lrhip_stage {
 // =====================================================================================================
 struct FmDiscrimStage : lrhip_stage {
     double gain = 1;
-    DeviceBuf prev;     // two float2 slots, ping-pong
-    int cur = 0;
+    Carried<float2> prev;     // the last input sample of the previous call
     const char *kind() const override { return "fmdiscrim"; }
-    int reset() override { cur = 0; return zero_fill(prev, 4 * sizeof(float)); }
+    int reset() override { return prev.reset(); }
     long memory() const override { return 1; }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
         if (n > cap) return set_error("fmdiscrim: output capacity %lu < %lu", cap, n);
         if (!n) return 0;
-        float2 *p = (float2 *)prev.p;
         static const bool disc_vec2 = getenv("LRHIP_DISC_VEC2") != nullptr;      // A/B knob: the 8-byte-store form
         if (!disc_vec2 && (((uintptr_t)in_dev | (uintptr_t)out_dev) & 15) == 0)
             hipLaunchKernelGGL(fmdiscrim_vec4_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, ctx().stream, (const float2 *)in_dev, (float *)out_dev, n, 1.0 / gain,
-                               (const float2 *)(p + cur), p + (cur ^ 1));
+                               prev.in(), prev.out());
         else if ((((uintptr_t)in_dev & 15) | ((uintptr_t)out_dev & 7)) == 0)
             hipLaunchKernelGGL(fmdiscrim_vec2_kernel, dim3(grid_for(n / 2 + 1, 256)), dim3(256), 0, ctx().stream, (const float2 *)in_dev, (float *)out_dev, n, 1.0 / gain,
-                               (const float2 *)(p + cur), p + (cur ^ 1));
+                               prev.in(), prev.out());
         else
             hipLaunchKernelGGL(fmdiscrim_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const float2 *)in_dev, (float *)out_dev, n, 1.0 / gain,
-                               (const float2 *)(p + cur), p + (cur ^ 1));
+                               prev.in(), prev.out());
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        prev.flip();
         return (long)n;
     }
 };
 
 struct FmModStage : lrhip_stage {
     double k = 0;
-    DeviceBuf phase, tile_sum;     // phase: two uint64 slots, ping-pong
-    int cur = 0;
+    Carried<uint64_t> phase;       // the running phase, 64-bit fixed point
+    DeviceBuf tile_sum;
     const char *kind() const override { return "fmmod"; }
-    int reset() override { cur = 0; return zero_fill(phase, 2 * sizeof(uint64_t)); }
+    int reset() override { return phase.reset(); }
     long memory() const override { return -1; }      // the phase is the integral of the whole input
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
@@ -111,13 +109,13 @@ struct FmModStage : lrhip_stage {
         if (!n) return 0;
         unsigned long ntiles = (n + FMOD_TILE - 1) / FMOD_TILE;
         if (tile_sum.reserve(ntiles * sizeof(uint64_t))) return -1;
-        uint64_t *ph = (uint64_t *)phase.p, *ts = (uint64_t *)tile_sum.p;
+        uint64_t *ts = (uint64_t *)tile_sum.p;
         hipLaunchKernelGGL(fmod_tile_sum_kernel, dim3((unsigned)ntiles), dim3(256), 0, ctx().stream, (const float *)in_dev, n, k, ts);
-        hipLaunchKernelGGL(fmod_tile_scan_kernel, dim3(1), dim3(256), 0, ctx().stream, ts, ntiles, (const uint64_t *)(ph + cur), ph + (cur ^ 1));
+        hipLaunchKernelGGL(fmod_tile_scan_kernel, dim3(1), dim3(256), 0, ctx().stream, ts, ntiles, phase.in(), phase.out());
         hipLaunchKernelGGL(fmod_emit_kernel, dim3((unsigned)ntiles), dim3(256), 0, ctx().stream, (const float *)in_dev, (float2 *)out_dev, n, k,
                            (const uint64_t *)ts);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        phase.flip();
         return (long)n;
     }
 };

@@ -55,15 +55,10 @@ struct UnaryStage : lrhip_stage {
 
 struct DelayStage : lrhip_stage {
     unsigned long D = 1;
-    DeviceBuf state[2];
-    int cur = 0;
+    TwoSlots state;                    // the last D input samples
     const char *kind() const override { return "delay"; }
     long memory() const override { return (long)D; }
-    int reset() override
-    {
-        cur = 0;
-        return (zero_fill(state[0], D * in_size) || zero_fill(state[1], D * in_size)) ? -1 : 0;
-    }
+    int reset() override { return state.reset(D * in_size); }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
         if (n > cap) return set_error("delay: output capacity %lu < %lu", cap, n);
@@ -71,21 +66,19 @@ struct DelayStage : lrhip_stage {
         static const bool no_vec = getenv("LRHIP_ELEM_SCALAR") != nullptr;
         if (!no_vec && (D * in_size) % 16 == 0 && (n * in_size) % 16 == 0 && ((uintptr_t)in_dev % 16) == 0 && ((uintptr_t)out_dev % 16) == 0) {
             const unsigned long n4 = n * in_size / 16, D4 = D * in_size / 16;
-            hipLaunchKernelGGL(delay_vec_kernel, dim3(grid_for(n4 + D4, 256)), dim3(256), 0, ctx().stream, (const float4 *)state[cur].p, (const float4 *)in_dev,
-                               (float4 *)out_dev, (float4 *)state[cur ^ 1].p, n4, D4);
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-            return (long)n;
+            hipLaunchKernelGGL(delay_vec_kernel, dim3(grid_for(n4 + D4, 256)), dim3(256), 0, ctx().stream, state.in<float4>(), (const float4 *)in_dev,
+                               (float4 *)out_dev, state.out<float4>(), n4, D4);
+        } else if (in_size == 8) {
+            const unsigned grid = grid_for(n + D, 256);
+            hipLaunchKernelGGL(delay_kernel<float2>, dim3(grid), dim3(256), 0, ctx().stream, state.in<float2>(), (const float2 *)in_dev,
+                               (float2 *)out_dev, state.out<float2>(), n, D);
+        } else {
+            const unsigned grid = grid_for(n + D, 256);
+            hipLaunchKernelGGL(delay_kernel<float>, dim3(grid), dim3(256), 0, ctx().stream, state.in<float>(), (const float *)in_dev,
+                               (float *)out_dev, state.out<float>(), n, D);
         }
-        unsigned grid = grid_for(n + D, 256);
-        if (in_size == 8)
-            hipLaunchKernelGGL(delay_kernel<float2>, dim3(grid), dim3(256), 0, ctx().stream, (const float2 *)state[cur].p, (const float2 *)in_dev,
-                               (float2 *)out_dev, (float2 *)state[cur ^ 1].p, n, D);
-        else
-            hipLaunchKernelGGL(delay_kernel<float>, dim3(grid), dim3(256), 0, ctx().stream, (const float *)state[cur].p, (const float *)in_dev,
-                               (float *)out_dev, (float *)state[cur ^ 1].p, n, D);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        state.flip();
         return (long)n;
     }
 };

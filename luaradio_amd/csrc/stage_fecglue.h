@@ -70,14 +70,13 @@ static lrhip_stage_t *puncture_create(const char *op)
 struct ConvInterleaveStage : lrhip_stage {
     uint32_t I = 2, M = 1, D = 2, q = 0;
     bool deinterleave = false;
-    DeviceBuf carry[2];
-    int cur = 0;
+    TwoSlots carry;
     const char *kind() const override { return deinterleave ? "convdeinterleave" : "convinterleave"; }
     long memory() const override { return (long)D; }
     int seek_to(uint64_t n0)
     {
-        cur = 0; q = (uint32_t)(n0 % I);
-        return (zero_fill(carry[0], D) || zero_fill(carry[1], D)) ? -1 : 0;
+        q = (uint32_t)(n0 % I);
+        return carry.reset(D);
     }
     int reset() override { return seek_to(0); }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
@@ -98,14 +97,14 @@ struct ConvInterleaveStage : lrhip_stage {
         const size_t lds_bytes = ((size_t)T + D + 32 + 15) & ~(size_t)15;
         if (kernel_allow_lds(convinterleave_kernel, lds_bytes)) return -1;
         const unsigned long tiles = (n + 15 + T - 1) / T;
-        const uint8_t *carried = (const uint8_t *)carry[cur].p;
+        const uint8_t *carried = carry.in<uint8_t>();
         hipLaunchKernelGGL(convinterleave_kernel, dim3(grid_for(tiles, 1)), dim3(FG_NT), lds_bytes, ctx().stream, carried, (const uint8_t *)in_dev, (uint8_t *)out_dev,
                            I, M, D, (int)deinterleave, q, n, T, (int)(n < (1ul << 32)));
         LR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(frame_carry_kernel, dim3(grid_for(D, 256)), dim3(256), 0, ctx().stream, carried, (const uint8_t *)in_dev, (uint8_t *)carry[cur ^ 1].p, D,
+        hipLaunchKernelGGL(frame_carry_kernel, dim3(grid_for(D, 256)), dim3(256), 0, ctx().stream, carried, (const uint8_t *)in_dev, carry.out<uint8_t>(), D,
                            (uint64_t)n, D);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        carry.flip();
         q = (uint32_t)((q + n % I) % I);
         return (long)n;
     }

@@ -11,8 +11,8 @@ struct FirWinRealStage : lrhip_stage {
     int M = 0;
     bool iir = false;
     std::vector<float> taps_rev;
-    DeviceBuf d_taps, d_ptab, hist[2], st[2];      // st: {y[-1], v[-1]} ping-pong
-    int cur = 0;
+    DeviceBuf d_taps, d_ptab;
+    TwoSlots hist, st;                             // the last M - 1 inputs; {y[-1], v[-1]}: each its own pair, flipped together
     float b0 = 0.f, b1 = 0.f, na1 = 0.f;
     int nb = 1, warm_waves = 4;
     unsigned long D = 1, index = 0;
@@ -30,10 +30,8 @@ struct FirWinRealStage : lrhip_stage {
     unsigned long align() const override { return iir ? (unsigned long)FWR_TILE : 1UL; }
     int reset() override
     {
-        cur = 0; index = 0;
-        for (int i = 0; i < 2; i++)
-            if (zero_fill(hist[i], sizeof(float) * (size_t)(M > 1 ? M - 1 : 1)) || zero_fill(st[i], 4 * sizeof(float))) return -1;
-        return 0;
+        index = 0;
+        return (hist.reset(sizeof(float) * (size_t)(M > 1 ? M - 1 : 1)) || st.reset(4 * sizeof(float))) ? -1 : 0;
     }
     static bool supported_taps(int m) { return m == 32 || m == 64 || m == 128; }
     // is the recurrence's memory short enough for the in-launch warm-up?  |a1|^(1024 w) < 1e-12 for w in {1, 2, 4}
@@ -57,18 +55,19 @@ struct FirWinRealStage : lrhip_stage {
         if (II && run < 2 && ntiles > slots / 2) run = 2;          // bound the warm-up share
         FwrParams pr;
         memset(&pr, 0, sizeof(pr));
-        pr.hist = (const float *)hist[cur].p; pr.x = x; pr.n = n; pr.taps_rev = (const float *)d_taps.p; pr.y = y;
-        pr.hist_out = M > 1 ? (float *)hist[cur ^ 1].p : nullptr;
+        pr.hist = hist.in<float>(); pr.x = x; pr.n = n; pr.taps_rev = (const float *)d_taps.p; pr.y = y;
+        pr.hist_out = M > 1 ? hist.out<float>() : nullptr;
         pr.run = run;
         pr.b0 = b0; pr.b1 = b1; pr.na1 = na1; pr.nb = nb; pr.ptab = (const float *)d_ptab.p;
-        const float *si = (const float *)st[cur].p;
-        float *so = (float *)st[cur ^ 1].p;
+        const float *si = st.in<float>();
+        float *so = st.out<float>();
         pr.state_in = si; pr.vhist = si + 1; pr.state_out = so; pr.vhist_out = so + 1;
         pr.dec = (long)D; pr.dfirst = (long)index; pr.warm_waves = warm_waves;
         const unsigned grid = (unsigned)((ntiles + run - 1) / run);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, pr);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();                                               // (with M == 1 no history is written: nothing reads it either)
+        st.flip();
         return 0;
     }
     template <bool II>

@@ -14,8 +14,8 @@ struct IirStage : lrhip_stage {
     std::vector<double> Ttile;            // A^TILE in double (row-major PxP) for the per-launch carry powers
     int warm_tiles = 0;                   // > 0: A^(warm_tiles*TILE) underflows Float32 -> single-launch iir_stream_kernel
     int warm_chunks = 0;                  // > 0 (first order): |p|^(16 warm_chunks) < 1e-12 with at most half a tile -> one-shot launch, a workgroup per tile
-    DeviceBuf xhist[2], state[2], tile_end, tile_start, seq_xs, seq_ys;
-    int cur = 0;
+    TwoSlots xhist, state;                // the last inputs and the recurrence state of the scan forms: each its own pair, flipped together
+    DeviceBuf tile_end, tile_start, seq_xs, seq_ys;
     unsigned long D = 1, index = 0;       // fused DownsamplerBlock behind the filter (chains)
     const char *kind() const override { return "iir"; }
     unsigned long max_output(unsigned long n) const override { return D == 1 ? n : n / D + 1; }
@@ -32,11 +32,8 @@ struct IirStage : lrhip_stage {
     unsigned long align() const override { return scan ? (unsigned long)IIR_TILE : 1UL; }
     int reset() override
     {
-        cur = 0; index = 0;
-        for (int i = 0; i < 2; i++) {
-            if (zero_fill(xhist[i], sizeof(float) * S * IIR_MAX_NB)) return -1;
-            if (zero_fill(state[i], sizeof(float) * S * (IIR_MAX_P + 1))) return -1;
-        }
+        index = 0;
+        if (xhist.reset(sizeof(float) * S * IIR_MAX_NB) || state.reset(sizeof(float) * S * (IIR_MAX_P + 1))) return -1;
         if (zero_fill(seq_xs, sizeof(float) * S * IIR_SEQ_MAX) || zero_fill(seq_ys, sizeof(float) * S * IIR_SEQ_MAX)) return -1;
         return 0;
     }
@@ -45,8 +42,8 @@ struct IirStage : lrhip_stage {
     {
         using ST = typename IirScanT<PP>::T;
         long ntiles = (n + IIR_TILE - 1) / IIR_TILE;
-        const float *xh = (const float *)xhist[cur].p, *st = (const float *)state[cur].p;
-        float *st_out = (float *)state[cur ^ 1].p;
+        const float *xh = xhist.in<float>(), *st = state.in<float>();
+        float *st_out = state.out<float>();
         const ST *tp = (const ST *)d_tpow.p;
         if (warm_tiles > 0) {
             // tiles per workgroup: enough workgroups to fill the chip a few times over, at most 8 tiles each
@@ -71,9 +68,8 @@ struct IirStage : lrhip_stage {
             }
             unsigned grid = (unsigned)((ntiles + run - 1) / run);
             hipLaunchKernelGGL((iir_stream_kernel<SS, PP, NBT>), dim3(grid), dim3(256), 0, ctx().stream, x, y, n, xh, st, st_out, (long)D, (long)index, run,
-                               wc ? 1 : warm_tiles, wc, co, (float *)xhist[cur ^ 1].p, tp, (no_coal ? 1 : 0) | (plain_st ? 2 : 0));
+                               wc ? 1 : warm_tiles, wc, co, xhist.out<float>(), tp, (no_coal ? 1 : 0) | (plain_st ? 2 : 0));
             LR_LAUNCH_CHECK();
-            cur ^= 1;
             return 0;
         }
         if (tile_end.reserve(sizeof(ST) * ntiles * SS * PP) || tile_start.reserve(sizeof(ST) * ntiles * SS * PP) ||
@@ -93,10 +89,9 @@ struct IirStage : lrhip_stage {
                            (const ST *)tile_start.p, (ST *)nullptr, st, st_out, (long)D, (long)index, co, tp);
         LR_LAUNCH_CHECK();
         if (nb > 1) {
-            hipLaunchKernelGGL(iir_state_kernel<SS>, dim3(1), dim3(64), 0, ctx().stream, x, n, nb, xh, (float *)xhist[cur ^ 1].p);
+            hipLaunchKernelGGL(iir_state_kernel<SS>, dim3(1), dim3(64), 0, ctx().stream, x, n, nb, xh, xhist.out<float>());
             LR_LAUNCH_CHECK();
         }
-        cur ^= 1;
         return 0;
     }
     template <int SS, int PP>
@@ -126,12 +121,15 @@ struct IirStage : lrhip_stage {
             if (S == 1) switch (P) { LR_IIR_P(1, 1); LR_IIR_P(1, 2); LR_IIR_P(1, 3); LR_IIR_P(1, 4); LR_IIR_P(1, 5); LR_IIR_P(1, 6); LR_IIR_P(1, 7); default: rc = run_scan<1, 8>(x, y, (long)n); }
             else switch (P) { LR_IIR_P(2, 1); LR_IIR_P(2, 2); LR_IIR_P(2, 3); LR_IIR_P(2, 4); LR_IIR_P(2, 5); LR_IIR_P(2, 6); LR_IIR_P(2, 7); default: rc = run_scan<2, 8>(x, y, (long)n); }
 #undef LR_IIR_P
+            if (rc) return rc;
+            // the one commit of the scan forms, whichever ran (with nb <= 1 the three-pass form leaves xhist.out() unwritten: nothing reads it)
+            xhist.flip();
+            state.flip();
         } else {
             if (S == 1) hipLaunchKernelGGL(iir_seq_kernel<1>, dim3(1), dim3(64), 0, ctx().stream, x, y, (long)n, seq, (float *)seq_xs.p, (float *)seq_ys.p);
             else hipLaunchKernelGGL(iir_seq_kernel<2>, dim3(1), dim3(64), 0, ctx().stream, x, y, (long)n, seq, (float *)seq_xs.p, (float *)seq_ys.p);
             LR_LAUNCH_CHECK();
         }
-        if (rc) return rc;
         if (D > 1) index = index + n_out * D - n;       // downsampler.lua:53
         return (long)n_out;
     }
@@ -225,33 +223,32 @@ struct AgcStage : lrhip_stage {
     AgcParams p;
     int S = 1;
     bool squelch = false;                              // PowerSquelchBlock: power scan + gate only
-    DeviceBuf state, mapsP, mapsG, startP, startG;     // state: two (P, G) double pairs, ping-pong
-    int cur = 0;
+    Carried<double[2]> state;                          // (P, G): the power estimate and the gain
+    DeviceBuf mapsP, mapsG, startP, startG;
     const char *kind() const override { return "agc"; }
     long memory() const override { return -1; }
-    int reset() override { cur = 0; return zero_fill(state, 4 * sizeof(double)); }
+    int reset() override { return state.reset(); }
     template <int SS>
     int go(const float *x, float *y, unsigned long n)
     {
         unsigned long nt = (n + AGC_TILE - 1) / AGC_TILE;
         if (mapsP.reserve(nt * 2 * sizeof(double)) || mapsG.reserve(nt * 2 * sizeof(double)) || startP.reserve(nt * sizeof(double)) ||
             startG.reserve(nt * sizeof(double))) return -1;
-        double *st = (double *)state.p + 2 * cur, *st_out = (double *)state.p + 2 * (cur ^ 1);
+        const double *st = *state.in();
+        double *st_out = *state.out();
         double *mp = (double *)mapsP.p, *mg = (double *)mapsG.p, *sp = (double *)startP.p, *sg = (double *)startG.p;
         dim3 g((unsigned)nt), b(256);
         hipLaunchKernelGGL((agc_pass_kernel<SS, 0>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
-        hipLaunchKernelGGL(agc_carry_kernel, dim3(1), b, 0, ctx().stream, (const double *)mp, nt, (const double *)st, sp);
+        hipLaunchKernelGGL(agc_carry_kernel, dim3(1), b, 0, ctx().stream, (const double *)mp, nt, st, sp);
         if (squelch) {
             hipLaunchKernelGGL((agc_pass_kernel<SS, 3>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-            return 0;
+        } else {
+            hipLaunchKernelGGL((agc_pass_kernel<SS, 1>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
+            hipLaunchKernelGGL(agc_carry_kernel, dim3(1), b, 0, ctx().stream, (const double *)mg, nt, st + 1, sg);
+            hipLaunchKernelGGL((agc_pass_kernel<SS, 2>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
         }
-        hipLaunchKernelGGL((agc_pass_kernel<SS, 1>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
-        hipLaunchKernelGGL(agc_carry_kernel, dim3(1), b, 0, ctx().stream, (const double *)mg, nt, (const double *)(st + 1), sg);
-        hipLaunchKernelGGL((agc_pass_kernel<SS, 2>), g, b, 0, ctx().stream, x, y, n, p, mp, mg, (const double *)sp, (const double *)sg, st_out);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        state.flip();
         return 0;
     }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override

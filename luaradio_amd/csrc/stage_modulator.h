@@ -8,13 +8,14 @@ struct ModStage : lrhip_stage {
     unsigned P = 1;
     int b = 1, msb = 1;
     bool qam = false;
-    DeviceBuf d_table, carry;                // d_table: 2^b entries, Float32 (pam) or interleaved ComplexFloat32 (qam); carry: two slots of MOD_MAX_BITS bytes (ping-pong with `cur`)
-    int cur = 0, pend = 0;                   // pend: bits carried from the calls so far (< b)
+    DeviceBuf d_table;                       // 2^b entries, Float32 (pam) or interleaved ComplexFloat32 (qam)
+    Carried<uint8_t[MOD_MAX_BITS]> carry;    // the pending bits, a byte each
+    int pend = 0;                            // bits carried from the calls so far (< b)
     const char *kind() const override { return qam ? "qam" : "pam"; }
     int reset() override
     {
-        cur = 0; pend = 0;
-        return zero_fill(carry, 2 * MOD_MAX_BITS);
+        pend = 0;
+        return carry.reset();
     }
     // a call completes at most ceil(n / b) symbols whatever is pending
     unsigned long max_output(unsigned long n) const override { return ((n + (unsigned long)b - 1) / (unsigned long)b) * P; }
@@ -31,8 +32,8 @@ struct ModStage : lrhip_stage {
     template <typename T, int PER>
     int launch(const uint8_t *x, const ModParams &p, void *out_dev, unsigned long n_out)
     {
-        const uint8_t *ci = (const uint8_t *)carry.p + cur * MOD_MAX_BITS;
-        uint8_t *co = (uint8_t *)carry.p + (cur ^ 1) * MOD_MAX_BITS;
+        const uint8_t *ci = *carry.in();
+        uint8_t *co = *carry.out();
         const T *tab = (const T *)d_table.p;
         if ((uintptr_t)out_dev % 16) {
             hipLaunchKernelGGL(mod_scalar_kernel<T>, dim3(grid_for(n_out, 256)), dim3(256), 0, ctx().stream, x, ci, co, tab, (T *)out_dev, p, n_out);
@@ -57,7 +58,7 @@ struct ModStage : lrhip_stage {
         const int rc = qam ? launch<float2, 2>((const uint8_t *)in_dev, p, out_dev, n_out) : launch<float, 4>((const uint8_t *)in_dev, p, out_dev, n_out);
         if (rc) return rc;
         pend = (int)((unsigned long)pend + n - nsym * (unsigned long)b);
-        cur ^= 1;
+        carry.flip();
         return (long)n_out;
     }
 };

@@ -10,8 +10,8 @@ struct PfbChannelizerStage : lrhip_stage {
     int seek(unsigned long long, unsigned long long *) override { return set_error("seek: not supported by the channelizer stage"); }
     long memory() const override { return -1; }
     int M = 0, K = 0, log2k = 0, P = 0, R = 1, D = 0;
-    DeviceBuf taps, tw, hist[2];
-    int cur = 0;
+    DeviceBuf taps, tw;
+    TwoSlots hist;                   // the last M - 1 input samples
     unsigned long index = 0;
     unsigned phase = 0;              // frames emitted so far modulo R
     const char *kind() const override { return "pfb_channelizer"; }
@@ -34,9 +34,8 @@ struct PfbChannelizerStage : lrhip_stage {
     int frames_per_group() const { return K <= 1024 ? frames_per_tile() : PFB_SCRATCH / K; }
     int reset() override
     {
-        cur = 0; index = 0; phase = 0;
-        size_t hb = (size_t)(M - 1) * 2 * sizeof(float);
-        return (zero_fill(hist[0], hb) || zero_fill(hist[1], hb)) ? -1 : 0;
+        index = 0; phase = 0;
+        return hist.reset((size_t)(M - 1) * 2 * sizeof(float));
     }
     template <int F, int NT>
     int launch(const float *x, long n, float *y, long nframes)
@@ -46,7 +45,7 @@ struct PfbChannelizerStage : lrhip_stage {
         auto kern = pfb_channelizer_kernel<F, NT>;
         if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + T - 1) / T);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)taps.p,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, hist.in<float>(), x, (const float *)taps.p,
                            (const float2 *)tw.p, y, M, log2k, P, T, G, n, nframes, (long)index);
         LR_LAUNCH_CHECK();
         return 0;
@@ -59,7 +58,7 @@ struct PfbChannelizerStage : lrhip_stage {
         auto kern = pfb_oversampled_kernel<RR, F, NT>;
         if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + T - 1) / T);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)taps.p,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds_bytes, ctx().stream, hist.in<float>(), x, (const float *)taps.p,
                            (const float2 *)tw.p, y, M, log2k, P, T, G, n, nframes, (long)index, (int)phase);
         LR_LAUNCH_CHECK();
         return 0;
@@ -103,9 +102,9 @@ struct PfbChannelizerStage : lrhip_stage {
             if (rc) return rc;
         }
         unsigned grid = grid_for((unsigned long)(M - 1) * 2, 256);
-        hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, (const float *)hist[cur].p, x, (float *)hist[cur ^ 1].p, M, n);
+        hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, hist.in<float>(), x, hist.out<float>(), M, n);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();
         index = index + (unsigned long)nframes * D - n_in;
         phase = (unsigned)((phase + nframes) % R);
         return nframes * K;

@@ -6,22 +6,21 @@
 struct PhaseCorrStage : lrhip_stage {
     PcParams p;
     bool real_out = false;
-    DeviceBuf state, ring, scratch;          // state: PcState ping-pong; ring: the last N q, slot = measurement index mod N
-    int cur = 0;
+    Carried<PcState> state;
+    DeviceBuf ring, scratch;                 // ring: the last N q, slot = measurement index mod N
     unsigned long long off = 0;              // host mirror of PcState.off (it depends on the call lengths only): sizes the measurement passes
     const char *kind() const override { return real_out ? "binaryphasecorrector+complextoreal" : "binaryphasecorrector"; }
     // a partition seeked to s measures at the multiples of I from s on; from s + N I on every window holds measurements made after s
     long memory() const override { return (long)(p.N * p.I); }
     int start(unsigned long long first_off)
     {
-        PcState s[2];
-        memset(s, 0, sizeof(s));
-        s[0].off = s[1].off = first_off;
-        s[0].rot[0] = s[1].rot[0] = (float)cos(-0.0);       // phi_moving_average = 0.0 (binaryphasecorrector.lua:38): (1, -0)
-        s[0].rot[1] = s[1].rot[1] = (float)sin(-0.0);
-        cur = 0;
+        PcState s;
+        memset(&s, 0, sizeof(s));
+        s.off = first_off;
+        s.rot[0] = (float)cos(-0.0);                        // phi_moving_average = 0.0 (binaryphasecorrector.lua:38): (1, -0)
+        s.rot[1] = (float)sin(-0.0);
         off = first_off;
-        if (upload(state, s, sizeof(s))) return -1;
+        if (state.reset(s)) return -1;
         return zero_fill(ring, (size_t)p.N * sizeof(unsigned long long));
     }
     int reset() override { return start(0); }
@@ -44,8 +43,8 @@ struct PhaseCorrStage : lrhip_stage {
                            *nan_at = (unsigned long long *)(sp + o_at);
         float2 *rot = (float2 *)(sp + o_rot);
         unsigned long long *rg = (unsigned long long *)ring.p;
-        const PcState *si = (const PcState *)state.p + cur;
-        PcState *so = (PcState *)state.p + (cur ^ 1);
+        const PcState *si = state.in();
+        PcState *so = state.out();
         const float2 *x = (const float2 *)in_dev;
         if (M) {
             hipLaunchKernelGGL(pc_measure_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, M, p, si, (const unsigned long long *)rg, Q, t_sum, t_nan);
@@ -71,7 +70,7 @@ struct PhaseCorrStage : lrhip_stage {
         else LR_PC(1, false);
 #undef LR_PC
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        state.flip();
         off = off + M * p.I - n;
         return (long)n;
     }

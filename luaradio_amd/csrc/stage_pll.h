@@ -11,35 +11,38 @@ struct PllStage : lrhip_stage {
     int port = PLL_PORT_OUT;
     unsigned long W = 0, seg_req = 0;        // warm-up length (0: none, serial only); "segment=" (0: chosen per call)
     bool allow = true;                       // "speculate=0" clears it
-    DeviceBuf state, scratch;                // state: PllState ping-pong, then PllStats
+    Carried<PllState> state;
+    DeviceBuf stats_buf, scratch;            // stats_buf: PllStats (two counters)
     PinnedBuf h_rej;
-    int cur = 0;
     const char *kind() const override { return port == PLL_PORT_OUT ? "pll" : "pll(error)"; }
     long memory() const override { return -1; }
     int reset() override
     {
-        PllState s[3];
-        memset(s, 0, sizeof(s));                             // the third slot holds PllStats (two counters)
-        s[0] = s[1] = pll_initial(p);
-        cur = 0;
-        return upload(state, s, sizeof(s));
+        return (state.reset(pll_initial(p)) || zero_fill(stats_buf, sizeof(PllStats))) ? -1 : 0;
     }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
         if (n > cap) return set_error("%s: output capacity %lu < %lu", kind(), cap, n);
         if (!n) return 0;
         const PllPlan q = pll_make_plan(n, p, W, (unsigned long)ctx().num_cus * 512, seg_req, allow);
-        const PllState *si = (const PllState *)state.p + cur;
-        PllState *so = (PllState *)state.p + (cur ^ 1);
-        PllStats *stats = (PllStats *)((PllState *)state.p + 2);
         const float *x = (const float *)in_dev;
-        if (!q.speculate) {
-            if (port == PLL_PORT_OUT) hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_OUT>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, si, out_dev, so, stats);
-            else hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_ERROR>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, si, out_dev, so, stats);
+        if (q.speculate) {
+            if (speculated(x, n, q, out_dev)) return -1;
+        } else {
+            PllStats *stats = (PllStats *)stats_buf.p;
+            if (port == PLL_PORT_OUT) hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_OUT>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, state.in(), out_dev, state.out(), stats);
+            else hipLaunchKernelGGL((pll_serial_kernel<PLL_PORT_ERROR>), dim3(1), dim3(64), 0, ctx().stream, x, n, p, state.in(), out_dev, state.out(), stats);
             LR_LAUNCH_CHECK();
-            cur ^= 1;
-            return (long)n;
         }
+        state.flip();                                        // the one commit, whichever path ran
+        return (long)n;
+    }
+    // the speculative path: 4 launches, 5 when the verify pass rejected a segment
+    int speculated(const float *x, unsigned long n, const PllPlan &q, void *out_dev)
+    {
+        const PllState *si = state.in();
+        PllState *so = state.out();
+        PllStats *stats = (PllStats *)stats_buf.p;
         // scratch: entry and exit edges, phi_multiplied totals / entries, the segments' mean |err|, rejection flags
         const size_t o_exit = q.nseg * sizeof(PllEdge), o_pm = o_exit + q.nseg * sizeof(PllEdge), o_emean = o_pm + q.nseg * sizeof(double),
                      o_bad = o_emean + q.nseg * sizeof(double), total = o_bad + q.nseg;
@@ -72,8 +75,7 @@ struct PllStage : lrhip_stage {
             hipLaunchKernelGGL((pll_emit_kernel<PLL_PORT_ERROR>), dim3(lanes_grid), dim3(64), 0, ctx().stream, x, n, p, q.C, q.nseg, (const PllEdge *)entry,
                                (const double *)pm, out_dev, so);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
-        return (long)n;
+        return 0;
     }
 };
 

@@ -15,14 +15,15 @@ constexpr long long PS_MAX_B = 1ll << 21;
 struct PsStage : lrhip_stage {
     PsParams p{0, 0, 0, 0};
     std::vector<uint32_t> pre_bits;          // the preamble, bit k of word k / 32
-    DeviceBuf pre, hist, scratch;            // hist: two histories of B samples, alternating with st.cur
+    DeviceBuf pre, scratch;
+    TwoSlots hist;                           // the history of B samples, flipped together with st
     Carried<PsState> st;                     // SEARCHING, preamblesampler.lua:56-59
     const char *kind() const override { return "preamblesampler"; }
     long memory() const override { return -1; }
     int reset() override
     {
         if (upload(pre, pre_bits.data(), pre_bits.size() * sizeof(uint32_t)) || st.reset()) return -1;
-        return zero_fill(hist, 2 * (size_t)p.B * sizeof(float));      // the reference's buffer starts as zeros (:52)
+        return hist.reset((size_t)p.B * sizeof(float));               // the reference's buffer starts as zeros (:52)
     }
     // Output 0 of a frame is emitted at sample j*, output m >= 1 at j* + m T - 1: inside a frame consecutive emissions are T - 1 (m = 0 -> 1) or
     // T samples apart.  The last one is at s' - 1; the next frame's i* >= s' and its j* > i*, so its first emission is at s' + 1 or later: 2
@@ -45,8 +46,8 @@ struct PsStage : lrhip_stage {
         PsFrame *frames = sc.frames.in(scratch);
         const PsState *si = st.in();
         PsState *so = st.out();
-        const float *hi = (const float *)hist.p + (size_t)st.cur * (size_t)p.B;
-        float *ho = (float *)hist.p + (size_t)(st.cur ^ 1) * (size_t)p.B;
+        const float *hi = hist.in<float>();
+        float *ho = hist.out<float>();
         const float *x = (const float *)in_dev;
         hipLaunchKernelGGL(ps_match_kernel, dim3((unsigned)nt), dim3(256), 0, ctx().stream, x, hi, n, p, (const uint32_t *)pre.p, mask_m, mask_d, tile_m, tile_d);
         LR_LAUNCH_CHECK();
@@ -59,6 +60,7 @@ struct PsStage : lrhip_stage {
                            (float *)out_dev, cap);
         LR_LAUNCH_CHECK();
         st.flip();
+        hist.flip();
         PsState got;
         if (st.fetch(got)) return -1;
         if (got.overflow || got.count > bound) return set_error("preamblesampler: %llu outputs in %llu frames exceed the bound %lu (%lu frames)", got.count, got.frames, bound, max_frames);

@@ -11,8 +11,7 @@
 struct FramedStage : lrhip_stage {
     rsplan::Frame frame{1, 1};
     const char *who = "";
-    DeviceBuf carry[2];
-    int cur = 0;
+    TwoSlots carry;
     uint64_t Q = 0;
     const char *kind() const override { return who; }
     unsigned long max_output(unsigned long n) const override { return (unsigned long)rsplan::max_output(n, frame); }
@@ -27,8 +26,8 @@ struct FramedStage : lrhip_stage {
     // the carried bytes are zeros wherever the stream continues
     int seek_to(uint64_t n0)
     {
-        cur = 0; Q = n0;
-        return (zero_fill(carry[0], (size_t)frame.fi * in_size) || zero_fill(carry[1], (size_t)frame.fi * in_size)) ? -1 : 0;
+        Q = n0;
+        return carry.reset((size_t)frame.fi * in_size);
     }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
     {
@@ -51,16 +50,16 @@ struct FramedStage : lrhip_stage {
         if (n_out > cap) return set_error("%s: output capacity %lu < %lu", who, cap, n_out);
         if (!in_dev) return set_error("%s: null input buffer", who);
         if (n_out && !out_dev) return set_error("%s: null output buffer", who);
-        const uint8_t *carried = (const uint8_t *)carry[cur].p;
+        const uint8_t *carried = carry.in<uint8_t>();
         if (nf && launch(carried, (const uint8_t *)in_dev, (uint8_t *)out_dev, c, (long)nf)) return -1;
         const unsigned count = rsplan::carried(Q + n, frame);
         if (count) {
             const unsigned es = (unsigned)in_size;
             hipLaunchKernelGGL(frame_carry_kernel, dim3(grid_for(count * es, 256)), dim3(256), 0, ctx().stream, carried, (const uint8_t *)in_dev,
-                               (uint8_t *)carry[cur ^ 1].p, c * es, nf * frame.fi * es, count * es);
+                               carry.out<uint8_t>(), c * es, nf * frame.fi * es, count * es);
             LR_LAUNCH_CHECK();
         }
-        cur ^= 1;
+        carry.flip();
         Q += n;
         return (long)n_out;
     }

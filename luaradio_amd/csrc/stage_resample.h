@@ -9,8 +9,8 @@ struct ResampleStage : lrhip_stage {
     int S = 2, M = 0, L = 1, HQ = 0;
     unsigned long D = 1;
     float c = 1.f;
-    DeviceBuf d_taps, d_ttab, hist[2];
-    int cur = 0;
+    DeviceBuf d_taps, d_ttab;
+    TwoSlots hist;                    // the last HQ input samples
     uint64_t Q0 = 0, m0 = 0;          // absolute input samples consumed / outputs emitted so far
     int interp_J = 0;                 // > 0: the register-window interpolator kernel applies (kernels_interp.h), taps per phase
     // (L, D) pairs with a kept-phases instantiation (fir_rational_kernel): 128 taps, ComplexFloat32, gcd(L, D) = 1
@@ -43,9 +43,8 @@ struct ResampleStage : lrhip_stage {
     static bool fits(int M, int L, unsigned long D) { return L >= 1 && 256 * D / (unsigned long)L + (unsigned long)((M - 1) / L) + 4 <= (unsigned long)SPAN_MAX; }
     int reset() override
     {
-        cur = 0; Q0 = 0; m0 = 0;
-        size_t hb = (size_t)(HQ > 0 ? HQ : 1) * S * sizeof(float);
-        return (zero_fill(hist[0], hb) || zero_fill(hist[1], hb)) ? -1 : 0;
+        Q0 = 0; m0 = 0;
+        return hist.reset((size_t)(HQ > 0 ? HQ : 1) * S * sizeof(float));
     }
     long run(const void *in_dev, unsigned long n, void *out_dev, unsigned long cap) override
     {
@@ -55,8 +54,10 @@ struct ResampleStage : lrhip_stage {
         uint64_t m_end = (hi + D - 1) / D;                     // first m with m*D >= hi
         long n_out = (long)(m_end - m0);
         if ((unsigned long)n_out > cap) return set_error("resample: output capacity %lu < %ld", cap, n_out);
-        const float *h = (const float *)hist[cur].p;
-        float *ho = (float *)hist[cur ^ 1].p;
+        const float *h = hist.in<float>();
+        float *ho = hist.out<float>();
+        int rc;
+        static const bool no_rational = getenv("LRHIP_NO_RATIONAL_WIN") != nullptr;      // A/B knob: one output per thread (fir_resample_kernel)
         if (interp_J > 0 && D == 1 && ((uintptr_t)in_dev & 7) == 0 && ((uintptr_t)out_dev & 7) == 0) {
             // ComplexFloat32 Interpolator(L), 128 taps: a lane owns 5 input positions and all L phases (fir_interp_kernel)
             auto gi = [&](auto kern, size_t lds_bytes, int tq) -> int {
@@ -68,17 +69,9 @@ struct ResampleStage : lrhip_stage {
                 return 0;
             };
 #define LR_INTERP(LL, JJ) gi(fir_interp_kernel<LL, JJ>, (size_t)FipGeom<LL, JJ>::LDS_FLOATS * sizeof(float), FipGeom<LL, JJ>::TQ)
-            int rc = L == 2 ? LR_INTERP(2, 64) : L == 3 ? LR_INTERP(3, 43) : L == 4 ? LR_INTERP(4, 32) : LR_INTERP(5, 26);
+            rc = L == 2 ? LR_INTERP(2, 64) : L == 3 ? LR_INTERP(3, 43) : L == 4 ? LR_INTERP(4, 32) : LR_INTERP(5, 26);
 #undef LR_INTERP
-            if (rc) return rc;
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-            Q0 += n;
-            m0 = m_end;
-            return n_out;
-        }
-        static const bool no_rational = getenv("LRHIP_NO_RATIONAL_WIN") != nullptr;      // A/B knob: one output per thread (fir_resample_kernel)
-        if (!no_rational && interp_J > 0 && D > 1 && ((uintptr_t)in_dev & 7) == 0 && ((uintptr_t)out_dev & 7) == 0) {
+        } else if (!no_rational && interp_J > 0 && D > 1 && ((uintptr_t)in_dev & 7) == 0 && ((uintptr_t)out_dev & 7) == 0) {
             // ComplexFloat32 RationalResampler(L, D), 128 taps: only the kept (position, phase) pairs, register window (fir_rational_kernel)
             auto gr = [&](auto kern, size_t lds_bytes, int tq) -> int {
                 const long ntiles = ((long)n + (long)(Q0 % D) + tq - 1) / tq, slots = chip_slots(kern, 256, lds_bytes);
@@ -93,30 +86,25 @@ struct ResampleStage : lrhip_stage {
             // ((3,4) R = 4 / 8 / 12 -> 0.33 / 0.70 / 0.49 ms, (5,4) R = 4 / 8 -> 0.86 / 0.24): the LDS pipe was the bound.  With the taps in SGPRs
             // (FW_TAPS_SGPR, kernels_firwin.h) a sweep of R = D .. 4 D moves no shape by more than 5 % ((2,3) R = 3 / 6 / 9 / 12 -> 0.242 / 0.190 / 0.180 /
             // 0.187, (3,4) R = 4 / 8 / 12 / 16 -> 0.180 / 0.174 / 0.174 / 0.172, (3,2) 0.289-0.293 for R = 4 .. 10)
-            int rc = (L == 3 && D == 2) ? LR_RAT(3, 2, 43, 6) : (L == 2 && D == 3) ? LR_RAT(2, 3, 64, 9) : (L == 4 && D == 3) ? LR_RAT(4, 3, 32, 6)
+            rc = (L == 3 && D == 2) ? LR_RAT(3, 2, 43, 6) : (L == 2 && D == 3) ? LR_RAT(2, 3, 64, 9) : (L == 4 && D == 3) ? LR_RAT(4, 3, 32, 6)
                    : (L == 3 && D == 4) ? LR_RAT(3, 4, 43, 8) : (L == 5 && D == 4) ? LR_RAT(5, 4, 26, 8) : LR_RAT(4, 5, 32, 10);
 #undef LR_RAT
-            if (rc) return rc;
-            LR_LAUNCH_CHECK();
-            cur ^= 1;
-            Q0 += n;
-            m0 = m_end;
-            return n_out;
+        } else {
+            // per-workgroup input span: 256 outputs advance 256*D/L input samples, plus the (M-1)/L samples of filter memory
+            int span_cap = (int)(256 * D / (unsigned long)L) + (M - 1) / L + 4;
+            size_t lds_bytes = ((size_t)((((M - 1) / L + 1) * L + 3) & ~3) + (size_t)span_cap * S) * sizeof(float);
+            auto go = [&](auto kern) -> int {
+                if (kernel_allow_lds(kern, lds_bytes)) return -1;
+                unsigned grid = n_out > 0 ? (unsigned)((n_out + 255) / 256) : 1;
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_taps.p, (float *)out_dev, M, L,
+                                   (long)D, (long)n, n_out, m0, Q0, HQ, c, span_cap, ho);
+                return 0;
+            };
+            rc = S == 2 ? go(fir_resample_kernel<2>) : go(fir_resample_kernel<1>);
         }
-        // per-workgroup input span: 256 outputs advance 256*D/L input samples, plus the (M-1)/L samples of filter memory
-        int span_cap = (int)(256 * D / (unsigned long)L) + (M - 1) / L + 4;
-        size_t lds_bytes = ((size_t)((((M - 1) / L + 1) * L + 3) & ~3) + (size_t)span_cap * S) * sizeof(float);
-        auto go = [&](auto kern) -> int {
-            if (kernel_allow_lds(kern, lds_bytes)) return -1;
-            unsigned grid = n_out > 0 ? (unsigned)((n_out + 255) / 256) : 1;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, h, (const float *)in_dev, (const float *)d_taps.p, (float *)out_dev, M, L,
-                               (long)D, (long)n, n_out, m0, Q0, HQ, c, span_cap, ho);
-            return 0;
-        };
-        int rc = S == 2 ? go(fir_resample_kernel<2>) : go(fir_resample_kernel<1>);
         if (rc) return rc;
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();                                           // the one commit, whichever form ran
         Q0 += n;
         m0 = m_end;
         return n_out;
@@ -130,16 +118,15 @@ struct ChannelizerStage : lrhip_stage {
     int seek(unsigned long long, unsigned long long *) override { return set_error("seek: not supported by the channelizer stage"); }
     long memory() const override { return -1; }
     int M = 0, K = 0;
-    DeviceBuf W, hist[2];
-    int cur = 0;
+    DeviceBuf W;
+    TwoSlots hist;                    // the last M - 1 input samples
     unsigned long index = 0;
     const char *kind() const override { return "channelizer"; }
     unsigned long max_output(unsigned long n) const override { return (n / K + 1) * K; }
     int reset() override
     {
-        cur = 0; index = 0;
-        size_t hb = (size_t)(M - 1) * 2 * sizeof(float);
-        return (zero_fill(hist[0], hb) || zero_fill(hist[1], hb)) ? -1 : 0;
+        index = 0;
+        return hist.reset((size_t)(M - 1) * 2 * sizeof(float));
     }
     template <int NCT>
     int launch(const float *x, long n, float *y, long nframes)
@@ -151,7 +138,7 @@ struct ChannelizerStage : lrhip_stage {
         auto kern = channelizer_kernel<NCT>;
         if (kernel_allow_lds(kern, lds_bytes)) return -1;
         unsigned grid = (unsigned)((nframes + CHAN_MT - 1) / CHAN_MT);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, (const float *)hist[cur].p, x, (const float *)W.p, y, M, n,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds_bytes, ctx().stream, hist.in<float>(), x, (const float *)W.p, y, M, n,
                            nframes, (long)index);
         LR_LAUNCH_CHECK();
         return 0;
@@ -168,9 +155,9 @@ struct ChannelizerStage : lrhip_stage {
             if (rc) return rc;
         }
         unsigned grid = grid_for((unsigned long)(M - 1) * 2, 256);
-        hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, (const float *)hist[cur].p, x, (float *)hist[cur ^ 1].p, M, n);
+        hipLaunchKernelGGL(fir_history_kernel<2>, dim3(grid), dim3(256), 0, ctx().stream, hist.in<float>(), x, hist.out<float>(), M, n);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();
         index = index + (unsigned long)nframes * K - n_in;
         return nframes * K;
     }

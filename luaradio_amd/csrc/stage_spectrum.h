@@ -100,9 +100,9 @@ struct WelchStage : lrhip_stage {
     int N = 0, hop = 0;
     unsigned long P = 0;            // pending samples (< N once a frame could be cut)
     long count = 0;                 // frames accumulated
-    DeviceBuf pending[2], frames, spectra, partial, sum;
+    TwoSlots pending;               // the P samples behind the last frame start + hop (read only while P > 0)
+    DeviceBuf frames, spectra, partial, sum;
     PinnedBuf h_avg;
-    int cur = 0;
     const char *kind() const override { return "welch"; }
     unsigned long max_output(unsigned long) const override { return 0; }
     int clear()
@@ -112,8 +112,8 @@ struct WelchStage : lrhip_stage {
     }
     int reset() override
     {
-        P = 0; cur = 0;
-        if (pending[0].reserve((size_t)N * in_size) || pending[1].reserve((size_t)N * in_size)) return -1;
+        P = 0;
+        if (pending.reset((size_t)N * in_size)) return -1;
         return clear();
     }
     template <typename T>
@@ -121,7 +121,7 @@ struct WelchStage : lrhip_stage {
     {
         unsigned long total = P + n;
         unsigned long nf = total >= (unsigned long)N ? (total - N) / hop + 1 : 0;
-        const T *pend = (const T *)pending[cur].p;
+        const T *pend = pending.in<T>();
         if (nf) {
             const void *frames_in;
             if (P == 0 && hop == N) frames_in = x;             // contiguous frames: no gather
@@ -148,10 +148,10 @@ struct WelchStage : lrhip_stage {
         unsigned long start = nf * hop, left = total - start;
         if (left) {
             hipLaunchKernelGGL(welch_pending_kernel<T>, dim3((unsigned)((left + 255) / 256)), dim3(256), 0, ctx().stream, pend, P, x, start,
-                               (T *)pending[cur ^ 1].p, left);
+                               pending.out<T>(), left);
             LR_LAUNCH_CHECK();
         }
-        cur ^= 1;
+        pending.flip();
         P = left;
         return 0;
     }

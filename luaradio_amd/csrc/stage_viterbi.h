@@ -43,13 +43,12 @@ static bool vit_read_code(const OpFields &f, VitCode &code)
 // Carried: the last K - 1 input bits (two slots of 8 bytes, ping-pong, written by the kernel).  One input bit gives n output bits
 struct ConvEncStage : lrhip_stage {
     VitCode code{};
-    DeviceBuf hist;
-    int cur = 0;
+    Carried<uint8_t[8]> hist;
     const char *kind() const override { return "convenc"; }
     unsigned long max_output(unsigned long n) const override { return n > ~0ul / (unsigned long)code.n ? ~0ul : n * (unsigned long)code.n; }
     long memory() const override { return code.K - 1; }
     void rate(unsigned long *num, unsigned long *den) const override { *num = 1; *den = (unsigned long)code.n; }
-    int reset() override { cur = 0; return zero_fill(hist, 16); }
+    int reset() override { return hist.reset(); }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
     {
         if (n0 > ~0ull / (unsigned long long)code.n) return set_error("convenc: seek to input %llu lies behind output 2^64", n0);
@@ -65,11 +64,10 @@ struct ConvEncStage : lrhip_stage {
         if (n_out > cap) return set_error("convenc: output capacity %lu < %lu", cap, n_out);
         if (!in_dev) return set_error("convenc: null input buffer");
         if (!out_dev) return set_error("convenc: null output buffer");
-        uint8_t *h = (uint8_t *)hist.p;
-        hipLaunchKernelGGL(convenc_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const uint8_t *)h + 8 * cur, (const uint8_t *)in_dev,
-                           (uint8_t *)out_dev, n, code, h + 8 * (cur ^ 1));
+        hipLaunchKernelGGL(convenc_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ctx().stream, (const uint8_t *)*hist.in(), (const uint8_t *)in_dev,
+                           (uint8_t *)out_dev, n, code, (uint8_t *)*hist.out());
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        hist.flip();
         return (long)n_out;
     }
 };
@@ -95,8 +93,7 @@ struct ViterbiStage : lrhip_stage {
     vitplan::Shape shape{};
     bool soft = true;
     float scale = 8.0f;
-    DeviceBuf carry[2];
-    int cur = 0;
+    TwoSlots carry;
     uint64_t Q = 0, done = 0;
     const char *kind() const override { return "viterbi"; }
     unsigned long max_output(unsigned long n) const override { return (unsigned long)vitplan::max_output(n, shape); }
@@ -106,9 +103,8 @@ struct ViterbiStage : lrhip_stage {
     // the carried inputs are erasures, q = 0, wherever the stream continues
     int seek_to(uint64_t n0)
     {
-        cur = 0; Q = n0; done = vitplan::windows_done(n0, shape);
-        const size_t bytes = vitplan::carry_capacity(shape);
-        return (zero_fill(carry[0], bytes) || zero_fill(carry[1], bytes)) ? -1 : 0;
+        Q = n0; done = vitplan::windows_done(n0, shape);
+        return carry.reset(vitplan::carry_capacity(shape));
     }
     int seek(unsigned long long n0, unsigned long long *n0_out) override
     {
@@ -129,7 +125,7 @@ struct ViterbiStage : lrhip_stage {
             const long slots = chip_slots(kern, 64 * waves, lds_bytes);
             if (slots < 0) return -1;
             const unsigned grid = persistent_grid((nw + waves - 1) / waves, slots, 0);      // a wave strides through the windows
-            hipLaunchKernelGGL(kern, dim3(grid ? grid : 1), dim3(64 * waves), lds_bytes, ctx().stream, (const int8_t *)carry[cur].p, in_dev, (uint8_t *)out_dev, code,
+            hipLaunchKernelGGL(kern, dim3(grid ? grid : 1), dim3(64 * waves), lds_bytes, ctx().stream, carry.in<int8_t>(), in_dev, (uint8_t *)out_dev, code,
                                shape, base, Q, (long)n, done, nw, chunks_max, scale);
             return 0;
         };
@@ -155,12 +151,12 @@ struct ViterbiStage : lrhip_stage {
         }
         const unsigned count = (unsigned)(Q + n - base1);                         // below carry_capacity (viterbi_plan.h)
         auto carry_on = [&](auto kern) {
-            hipLaunchKernelGGL(kern, dim3(grid_for(count, 256)), dim3(256), 0, ctx().stream, (const int8_t *)carry[cur].p, in_dev, (int8_t *)carry[cur ^ 1].p, base, Q,
+            hipLaunchKernelGGL(kern, dim3(grid_for(count, 256)), dim3(256), 0, ctx().stream, carry.in<int8_t>(), in_dev, carry.out<int8_t>(), base, Q,
                                (long)n, base1, count, scale);
         };
         if (soft) carry_on(viterbi_carry_kernel<true>); else carry_on(viterbi_carry_kernel<false>);
         LR_LAUNCH_CHECK();
-        cur ^= 1;
+        carry.flip();
         Q += n;
         done = done1;
         return (long)n_out;

@@ -316,7 +316,7 @@ def test_fir_kernel_form_table_on_the_cpu(tmp_path):
 
 
 def test_counted_stage_scratch_layouts_on_the_cpu(tmp_path):
-    """The stages with a data-dependent output count carve one scratch buffer into typed lists (luaradio_amd/csrc/stage_counted.h).  A wrong offset
+    """The stages with a data-dependent output count carve one scratch buffer into typed lists (luaradio_amd/csrc/stage_counted.h; what they carry between calls: stage_carry.h).  A wrong offset
     or a missed alignment shows only at a tile count where the padding matters, so tools/host_carve_check.hip walks the layouts the stages use
     - the same structs - over tile counts 1, 2, 3, 255, 256, 257 and frame bounds 1, 2 and an odd large one: in order, disjoint, aligned, covered."""
     import shutil
@@ -326,6 +326,22 @@ def test_counted_stage_scratch_layouts_on_the_cpu(tmp_path):
     exe = str(tmp_path / "host_carve_check")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"),
                         "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "host_carve_check.hip")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
+def test_carried_state_types_on_the_cpu(tmp_path):
+    """What a stage carries between calls lives in TwoSlots or Carried of luaradio_amd/csrc/stage_carry.h.  tools/host_carry_check.cpp drives that
+    header over exact-size host buffers: in() / out() are the two slots, flip() swaps them, reset() after an odd number of calls is the first slot
+    with both filled, the typed slots are adjacent, only fetch() pins a read-back buffer.  (The tool's header has the sanitizer build line.)"""
+    import shutil
+    gxx = shutil.which("g++")
+    if not gxx:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "host_carry_check")
+    r = subprocess.run([gxx, "-std=c++17", "-O1", "-g", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"), "-o", exe,
+                        os.path.join(ROOT, "tools", "host_carry_check.cpp")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr

@@ -13,6 +13,7 @@
 #include "kernels_varicode.h"
 using namespace lrhip;
 #include "stage.h"
+#include "stage_carry.h"
 #include "stage_counted.h"
 
 static int failures = 0;
