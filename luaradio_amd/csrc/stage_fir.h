@@ -2,6 +2,8 @@
 // (part of liblrhip.so; included by lrhip.hip in this order, one translation unit)
 #pragma once
 #include "fir_form.h"
+#include "fir_plan.h"
+#include "fir_tables.h"
 #include "launch_prep.h"
 
 // the kernel instantiation for a raw record format (RX_FMT_U8 / S8 / S16LE; kernels_fir.h): fn(std::integral_constant<int, RX_FMT_*>{}).  ComplexFloat32
@@ -869,317 +871,36 @@ struct FirStage : lrhip_stage, FirShape {      // (FirShape, fir_form.h: M, S, D
     }
 };
 
-// Tables of fir_decfft_kernel (layout: df_table_elems): 256-point twiddles, the D polyphase branch responses G_rho (1/256 of the
-// inverse transform folded in) in the lane order of the forward batches, and the output phasors e^{j w D k}.  All in double.
-// Window position j = D mm + rho of a block is input x[first + D m - r] with r = D - 1 - rho, so branch rho uses g_r[q] = g[D q + r],
-// g[i] = h[i] e^{-j w i}.
-static void decfft_build_tables(const float *taps, int M, int taps_complex, int D, double omega, std::vector<float> &out)
+static uint64_t turns_fixed(double omega);      // (stage_elem.h: a rotator's omega as 64-bit fixed-point turns per sample)
+// FIRFilterBlock as a stage: the request resolved into a shape (fir_plan.h) - refused there, before the device is touched - and the tables that shape
+// calls for built (fir_tables.h) and uploaded
+static FirStage *fir_build(const float *taps, unsigned ntaps, int taps_complex, int input_complex, unsigned decim, int use_fft, bool rot, double omega)
 {
-    const double PI2 = 6.283185307179586476925286766559;
-    const int A = D / 4, C = D % 4;
-    out.assign((size_t)df_table_elems(D) * 2, 0.f);
-    float *tw = out.data(), *Gf = tw + 2 * 256, *Gl = Gf + 2 * (size_t)A * 1024, *rt = Gl + 2 * (size_t)C * 256;
-    for (int k1 = 0; k1 < 16; k1++)
-        for (int u = 0; u < 16; u++) {
-            double a = -PI2 * (double)(k1 * u) / DF_N;
-            tw[2 * (k1 * 16 + u)] = (float)std::cos(a);
-            tw[2 * (k1 * 16 + u) + 1] = (float)std::sin(a);
-        }
-    long double turns = (long double)omega / (2.0L * 3.14159265358979323846264338327950288L);
-    turns -= floorl(turns);
-    std::vector<double> gr((size_t)M), gi((size_t)M);
-    for (int i = 0; i < M; i++) {
-        long double f = turns * (long double)i;
-        f -= floorl(f);
-        double a = -PI2 * (double)f, c = std::cos(a), sn = std::sin(a);
-        double hr = taps_complex ? taps[2 * i] : taps[i], hi = taps_complex ? taps[2 * i + 1] : 0.0;
-        gr[i] = hr * c - hi * sn;
-        gi[i] = hr * sn + hi * c;
+    const FirPlan p = fir_resolve({taps ? ntaps : 0, taps_complex, input_complex, decim, use_fft, rot});
+    if (p.refusal) { set_error("%s", p.refusal); return nullptr; }
+    std::unique_ptr<FirStage> q = new_stage<FirStage>();
+    if (!q) return nullptr;
+    q->M = (int)ntaps; q->S = input_complex ? 2 : 1; q->taps_complex = taps_complex; q->D = decim; q->rot = rot; q->in_size = q->out_size = 4 * q->S;
+    q->mode_req = p.mode_req; q->use_fft = p.use_fft; q->fft_arith = p.fft_arith; q->decfft = p.decfft; q->ctaps4 = p.ctaps4;
+    q->ksteps = p.ksteps; q->fft4k_V = p.fft4k_V; q->fft64_np = p.fft64_np; q->hist_pad = p.hist_pad; q->L = p.L;
+    if (rot) { q->rot_step = turns_fixed(omega); if (p.decfft) q->rot_omega = omega; }
+    q->taps_rev = fir_reversed_taps(taps, ntaps, taps_complex);
+    const auto up = [](DeviceBuf &b, const std::vector<float> &t) { return upload(b, t.data(), t.size() * sizeof(float)); };
+    const unsigned T = p.tables;      // (FIR_TAB_*; the uploads in the order they always had)
+    if (up(q->d_taps, q->taps_rev)) return nullptr;
+    if ((T & FIR_TAB_TOEPLITZ) && up(q->d_atab, fir_toeplitz_taps(q->taps_rev, q->M, (int)decim, p.ksteps))) return nullptr;
+    if ((T & FIR_TAB_CTAPS4) && up(q->d_ctaps4, fir_ctaps4_table(q->taps_rev, q->M))) return nullptr;
+    if ((T & FIR_TAB_TOEPLITZ_CC) && up(q->d_atab, fir_toeplitz_cc_taps(q->taps_rev, q->M, (int)decim, p.ksteps))) return nullptr;
+    if ((T & FIR_TAB_DECFFT) && up(q->d_dec_tables, fir_decfft_tables(taps, q->M, taps_complex, (int)decim, q->rot_omega))) return nullptr;
+    if ((T & FIR_TAB_FFT1024) && up(q->d_fft_tables, fir_fft1024_tables(taps, ntaps, taps_complex))) return nullptr;
+    if (T & FIR_TAB_FFT64) {      // 513 .. 1 281 taps: both 4096-point kernels read the one spectrum of all taps
+        std::vector<double> Hr, Hi;
+        taps_spectrum(taps, taps_complex, 0, ntaps, F4K_N, Hr, Hi);
+        if ((T & FIR_TAB_FFT4K) && up(q->d_fft4k_tables, fir_fft4k_tables(Hr, Hi))) return nullptr;
+        if (up(q->d_fft64_tables, fir_fft64_tables(Hr, Hi))) return nullptr;
     }
-    std::vector<double> Gr(DF_N), Gi(DF_N);
-    for (int rho = 0; rho < D; rho++) {
-        const int r = D - 1 - rho;
-        for (int k = 0; k < DF_N; k++) {
-            double sr = 0, si = 0;
-            for (int qq = 0; D * qq + r < M; qq++) {
-                double a = -PI2 * (double)((qq * k) % DF_N) / DF_N, c = std::cos(a), sn = std::sin(a);
-                sr += gr[D * qq + r] * c - gi[D * qq + r] * sn;
-                si += gr[D * qq + r] * sn + gi[D * qq + r] * c;
-            }
-            Gr[k] = sr / DF_N;
-            Gi[k] = si / DF_N;
-        }
-        for (int k2 = 0; k2 < 16; k2++)
-            for (int k1 = 0; k1 < 16; k1++) {
-                const int k = k1 + 16 * k2;
-                float *dst = rho < 4 * A ? Gf + 2 * ((size_t)(rho / 4) * 1024 + k2 * 64 + 16 * (rho % 4) + k1)
-                                         : Gl + 2 * ((size_t)(rho - 4 * A) * 256 + k2 * 16 + k1);
-                dst[0] = (float)Gr[k];
-                dst[1] = (float)Gi[k];
-            }
-    }
-    for (int w = 0; w < DF_N; w++) {
-        long double f = turns * (long double)D * (long double)w;
-        f -= floorl(f);
-        double a = PI2 * (double)f;
-        rt[2 * w] = (float)std::cos(a);
-        rt[2 * w + 1] = (float)std::sin(a);
-    }
-}
-
-static FirStage *fir_build(const float *taps, unsigned ntaps, int taps_complex, int input_complex, unsigned decim,
-                           int use_fft, bool rot, double omega)
-{
-    if (!taps || ntaps < 1) { set_error("fir: need at least one tap"); return nullptr; }
-    if (taps_complex && !input_complex) { set_error("fir: complex taps require ComplexFloat32 input (firfilter.lua:69-74)"); return nullptr; }
-    if (decim < 1) { set_error("fir: decimation must be >= 1"); return nullptr; }
-    const int mode_req = use_fft;
-    // decimating filters: overlap-save arithmetic exists in the polyphase form (kernels_firdecfft.h) for the complex stream
-    bool want_decfft = false;
-    if (decim > 1 && (use_fft == 2 || use_fft == 3)) {
-        // automatic (3) keeps the direct form for decimating filters: on MI355X the Toeplitz MFMA kernel is the faster one there
-        // (Tuner + discriminator, 2^26 samples: 0.155 ms against 0.165 ms, same box) and it is bit-exact
-        want_decfft = use_fft == 2 && FirStage::decfft_supported(decim, (int)ntaps, input_complex ? 2 : 1);
-        // "fast" is an arithmetic preference, not a framing: where no polyphase-FFT kernel exists for (taps, decimation) the direct form runs -
-        // stand-alone exactly as lrhip_chain_create does when it fuses filter and downsampler (one behaviour for both front doors)
-        use_fft = 0;
-    }
-    if (use_fft == 3) use_fft = (decim == 1 && !rot && ntaps >= 48 && ntaps <= 16 * FirStage::FFT_PART && (input_complex || !taps_complex)) ? 2 : 0;
-    if (use_fft && decim != 1) { set_error("fir: the reference's block-emission framing (use_fft = 1) cannot be combined with decimation"); return nullptr; }
-    if (use_fft < 0 || use_fft > 2) { set_error("fir: use_fft must be 0 (direct form), 1 (overlap-save as the reference: block emission), 2 (overlap-save arithmetic, sample-exact emission) or 3 (automatic)"); return nullptr; }
-    if (ntaps > (1u << 20)) { set_error("fir: too many taps"); return nullptr; }
-    if (ensure_init()) return nullptr;
-    std::unique_ptr<FirStage> q(new (std::nothrow) FirStage());
-    if (!q) { set_error("out of memory"); return nullptr; }
-    q->M = (int)ntaps; q->S = input_complex ? 2 : 1; q->taps_complex = taps_complex; q->D = decim; q->mode_req = mode_req;
-    q->use_fft = use_fft == 1; q->rot = rot;     // 1: reference emission framing; 2: FFT arithmetic, sample-exact emission
-    q->in_size = q->out_size = 4 * q->S;
-    int ts = taps_complex ? 2 : 1;
-    q->taps_rev.resize((size_t)ntaps * ts);
-    for (unsigned i = 0; i < ntaps; i++)
-        for (int c = 0; c < ts; c++) q->taps_rev[(size_t)i * ts + c] = taps[(size_t)(ntaps - 1 - i) * ts + c];
-    if (upload(q->d_taps, q->taps_rev.data(), q->taps_rev.size() * sizeof(float))) return nullptr;
-    if (!taps_complex && FirStage::mfma_supported_decim(decim)) {
-        int ks = fir_mfma_ksteps(q->M, (int)decim, q->S);
-        if ((size_t)fir_taps_len((int)decim, ks) * sizeof(float) <= 24 * 1024) {   // tap array must leave LDS room for the tile
-            std::vector<float> tab;
-            fir_mfma_build_taps(q->taps_rev.data(), q->M, (int)decim, ks, tab);
-            if (upload(q->d_atab, tab.data(), tab.size() * sizeof(float))) return nullptr;
-            q->ksteps = ks;
-        }
-    }
-    if (taps_complex && decim == 1 && input_complex && (ntaps == 16 || ntaps == 32)) {
-        // short complex filters as a streaming kernel (FirForm::WinShortC): (re, im, -im, re) per reversed tap
-        std::vector<float> t4((size_t)4 * ntaps);
-        for (unsigned j = 0; j < ntaps; j++) {
-            const float hr = q->taps_rev[2 * j], hi = q->taps_rev[2 * j + 1];
-            t4[4 * j] = hr; t4[4 * j + 1] = hi; t4[4 * j + 2] = -hi; t4[4 * j + 3] = hr;
-        }
-        if (upload(q->d_ctaps4, t4.data(), t4.size() * sizeof(float))) return nullptr;
-        q->ctaps4 = true;
-    }
-    if (taps_complex && decim <= 5) {
-        // taps'_re = interleave(hr_rev, -hi_rev), taps'_im = interleave(hi_rev, hr_rev) over the float stream
-        int M2 = 2 * q->M, D2 = 2 * (int)decim;
-        int ks = fir_mfma_ksteps(M2, D2, 1, 2);          // 8-B aligned complex input => float slack e in {0, 2}
-        if ((size_t)2 * fir_taps_len(D2, ks) * sizeof(float) <= 32 * 1024) {
-            std::vector<float> tre((size_t)M2), tim((size_t)M2), tab;
-            for (int j = 0; j < q->M; j++) {
-                float hr = q->taps_rev[2 * j], hi = q->taps_rev[2 * j + 1];
-                tre[2 * j] = hr; tre[2 * j + 1] = -hi;
-                tim[2 * j] = hi; tim[2 * j + 1] = hr;
-            }
-            std::vector<float> are, aim;
-            fir_mfma_build_taps(tre.data(), M2, D2, ks, are);
-            fir_mfma_build_taps(tim.data(), M2, D2, ks, aim);
-            tab = are;
-            tab.insert(tab.end(), aim.begin(), aim.end());
-            if (upload(q->d_atab, tab.data(), tab.size() * sizeof(float))) return nullptr;
-            q->ksteps = ks;
-            q->hist_pad = 1;
-        }
-    }
-    if (want_decfft) {
-        std::vector<float> tab;
-        decfft_build_tables(taps, (int)ntaps, taps_complex, (int)decim, rot ? omega : 0.0, tab);
-        if (upload(q->d_dec_tables, tab.data(), tab.size() * sizeof(float))) return nullptr;
-        q->decfft = true;
-        q->rot_omega = rot ? omega : 0.0;
-    }
-    if (rot) {
-        if (!q->decfft && !q->ksteps && !(input_complex && !taps_complex && (int)ntaps + 255 <= DECIM_SPAN_MAX)) {
-            set_error("fir: rotator fusion unavailable for this tap count / decimation");
-            return nullptr;
-        }
-        long double turns = (long double)omega / (2.0L * 3.14159265358979323846264338327950288L);
-        turns -= floorl(turns);
-        q->rot_step = (uint64_t)(turns * 18446744073709551616.0L);
-    }
-    if (use_fft && decim == 1 && !rot && ntaps >= 32 && ntaps <= 16 * FirStage::FFT_PART && (input_complex || !taps_complex)) {
-        // fused overlap-save kernel tables, one set per partition of <= FFT_PART taps: tw1[k1][t] | Hperm[4j+k3][lane] | tw2[k2][t2]
-        const double PI2 = 6.283185307179586476925286766559;
-        const int nparts = ((int)ntaps + FirStage::FFT_PART - 1) / FirStage::FFT_PART;
-        std::vector<float> tab((size_t)nparts * FFT_TABLE_ELEMS * 2);
-        for (int part = 0; part < nparts; part++) {
-            float *tp = tab.data() + (size_t)part * FFT_TABLE_ELEMS * 2;
-            const unsigned m0 = (unsigned)part * FirStage::FFT_PART, m1 = std::min<unsigned>(ntaps, m0 + FirStage::FFT_PART);
-            for (int k1 = 0; k1 < 16; k1++)
-                for (int t = 0; t < 64; t++) {
-                    double a = -PI2 * (double)((k1 * t) % FFTN) / FFTN;
-                    tp[2 * (k1 * 64 + t)] = (float)std::cos(a);
-                    tp[2 * (k1 * 64 + t) + 1] = (float)std::sin(a);
-                }
-            std::vector<double> Hr(FFTN, 0.0), Hi(FFTN, 0.0);
-            for (int k = 0; k < FFTN; k++) {
-                double sr = 0, si = 0;
-                for (unsigned m = m0; m < m1; m++) {
-                    double a = -PI2 * (double)((k * (long)(m - m0)) % FFTN) / FFTN, c = std::cos(a), sn = std::sin(a);
-                    double hr = taps_complex ? taps[2 * m] : taps[m], hi = taps_complex ? taps[2 * m + 1] : 0.0;
-                    sr += hr * c - hi * sn;
-                    si += hr * sn + hi * c;
-                }
-                Hr[k] = sr / FFTN;      // the 1/N of the inverse transform (spectrum_utils.lua:335-338) folded in
-                Hi[k] = si / FFTN;
-            }
-            for (int j = 0; j < 4; j++)
-                for (int k3 = 0; k3 < 4; k3++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        int qq = lane & 3, k1 = lane >> 2;
-                        int k = k1 + 16 * (4 * j + qq) + 256 * k3;
-                        size_t o = (size_t)16 * 64 + (size_t)(4 * j + k3) * 64 + lane;
-                        tp[2 * o] = (float)Hr[k];
-                        tp[2 * o + 1] = (float)Hi[k];
-#if LRHIP_FFT_E2_SWAP
-                        // fir_fft_kernel's numbering with the register <-> row transposes: q = the lane's row of 16, k1 = its position in the row
-                        const int qs = lane >> 4, k1w = lane & 15, ks = k1w + 16 * (4 * j + qs) + 256 * k3;
-                        const size_t os = (size_t)FFT_TABLE_HSW + (size_t)(4 * j + k3) * 64 + lane;
-                        tp[2 * os] = (float)Hr[ks];
-                        tp[2 * os + 1] = (float)Hi[ks];
-#endif
-                    }
-            for (int k2 = 0; k2 < 16; k2++)
-                for (int t2 = 0; t2 < 4; t2++) {
-                    double a = -PI2 * (double)((k2 * t2) % 64) / 64.0;
-                    size_t o = (size_t)2 * 16 * 64 + k2 * 4 + t2;
-                    tp[2 * o] = (float)std::cos(a);
-                    tp[2 * o + 1] = (float)std::sin(a);
-                }
-        }
-        if (upload(q->d_fft_tables, tab.data(), tab.size() * sizeof(float))) return nullptr;
-        q->fft_arith = true;
-        // (round 6: Float32 streams with real taps take the 64 x 64 kernel too - two stream blocks per transform; the workgroup-per-block kernel of small
-        // launches stays ComplexFloat32-only, small Float32 launches keep the partitioned kernel)
-        if ((input_complex || !taps_complex) && (int)ntaps > FirStage::FFT_PART && ntaps <= 1281) {
-            // tables of the 4096-point kernel (kernels_firfft4k.h): tw1 | tw2 | c[w][i] = W_64^(i w) | b[w][t] = W_4096^(t w) | H[w][16 x 64] of the bins w + 4 k'
-            std::vector<float> t4((size_t)F4K_TABLE_ELEMS * 2);
-            auto put = [&](size_t o, double a) { t4[2 * o] = (float)std::cos(a); t4[2 * o + 1] = (float)std::sin(a); };
-            for (int k1 = 0; k1 < 16; k1++)
-                for (int t = 0; t < 64; t++) put((size_t)k1 * 64 + t, -PI2 * (double)((k1 * t) % FFTN) / FFTN);
-            for (int k2 = 0; k2 < 16; k2++)
-                for (int t2 = 0; t2 < 4; t2++) put((size_t)16 * 64 + k2 * 4 + t2, -PI2 * (double)((k2 * t2) % 64) / 64.0);
-            for (int w = 0; w < 4; w++) {
-                for (int i = 0; i < 16; i++) put((size_t)16 * 64 + 64 + w * 16 + i, -PI2 * (double)((i * w) % 64) / 64.0);
-                for (int t = 0; t < 64; t++) put((size_t)F4K_TAB_B + w * 64 + t, -PI2 * (double)(t * w) / F4K_N);
-            }
-            std::vector<double> cs(F4K_N), sn(F4K_N), Hr(F4K_N), Hi(F4K_N);
-            for (int k = 0; k < F4K_N; k++) { cs[k] = std::cos(-PI2 * k / F4K_N); sn[k] = std::sin(-PI2 * k / F4K_N); }
-            for (int k = 0; k < F4K_N; k++) {
-                double sr = 0, si = 0;
-                for (unsigned m = 0; m < ntaps; m++) {
-                    const int a = (int)(((long)k * m) % F4K_N);
-                    const double hr = taps_complex ? taps[2 * m] : taps[m], hi = taps_complex ? taps[2 * m + 1] : 0.0;
-                    sr += hr * cs[a] - hi * sn[a];
-                    si += hr * sn[a] + hi * cs[a];
-                }
-                Hr[k] = sr / F4K_N;
-                Hi[k] = si / F4K_N;
-            }
-            for (int w = 0; w < 4; w++)
-                for (int j = 0; j < 4; j++)
-                    for (int k3 = 0; k3 < 4; k3++)
-                        for (int lane = 0; lane < 64; lane++) {
-                            const int qq = lane & 3, k1 = lane >> 2, kp = k1 + 16 * (4 * j + qq) + 256 * k3, k = w + 4 * kp;
-                            const size_t o = (size_t)F4K_TAB_H + (size_t)w * 1024 + (size_t)(4 * j + k3) * 64 + lane;
-                            t4[2 * o] = (float)Hr[k];
-                            t4[2 * o + 1] = (float)Hi[k];
-                        }
-            if (input_complex && upload(q->d_fft4k_tables, t4.data(), t4.size() * sizeof(float))) return nullptr;
-            // tables of the 64 x 64 form: C[c][t] = W_1024^(t c) | D[d][t] = W_4096^(t d) | H[r][l] = H(64 k1(r) + l) | Hsym[k1][l <= 32] = H(64 k1 + l)
-            std::vector<float> t6((size_t)F64_TABLE_ELEMS * 2, 0.f);
-            auto put6 = [&](size_t o, double a) { t6[2 * o] = (float)std::cos(a); t6[2 * o + 1] = (float)std::sin(a); };
-            for (int c = 0; c < 16; c++)
-                for (int t = 0; t < 64; t++) put6((size_t)c * 64 + t, -PI2 * (double)((c * t) % FFTN) / FFTN);
-            for (int d = 0; d < 4; d++)
-                for (int t = 0; t < 64; t++) put6((size_t)F64_TAB_D + d * 64 + t, -PI2 * (double)(t * d) / F4K_N);
-            for (int r = 0; r < 64; r++)
-                for (int l = 0; l < 64; l++) {
-                    const int k = 64 * f64_index(r) + l;
-                    const size_t o = (size_t)F64_TAB_H + (size_t)r * 64 + l;
-                    t6[2 * o] = (float)Hr[k];
-                    t6[2 * o + 1] = (float)Hi[k];
-                    if (l <= 32) {
-                        const size_t os = (size_t)F64_TAB_HSYM + (size_t)f64_index(r) * F64_HSYM_ROW + l;
-                        t6[2 * os] = (float)Hr[k];
-                        t6[2 * os + 1] = (float)Hi[k];
-                    }
-                }
-            if (upload(q->d_fft64_tables, t6.data(), t6.size() * sizeof(float))) return nullptr;
-            q->fft4k_V = (int)((ntaps - 1 + 255) / 256) * 256;
-            if (q->fft4k_V < 768) q->fft4k_V = 768;
-        }
-        if ((input_complex || !taps_complex) && ntaps > 1281 && ntaps <= 8193) {
-            // round 5: the 64 x 64 form at an overlap of 2 048 - one partition to 2 049 taps, two (taps [0, 2 048) and [2 048, ntaps)) above;
-            // round 6: three / four partitions of 2 048 taps (the last up to 2 049) to 8 193 taps - a second table set for the second launch
-            const int np = (int)((ntaps + 2046) / 2048);                      // ceil((ntaps - 1) / 2 048): 1 to 2 049 taps, 2 to 4 097, 3 to 6 145, 4 to 8 193
-            const int nsets = np > 2 ? 2 : 1;
-            std::vector<float> t6((size_t)F64_TABLE_ELEMS2 * 2 * nsets, 0.f);
-            auto put6 = [&](size_t o, double a) { t6[2 * o] = (float)std::cos(a); t6[2 * o + 1] = (float)std::sin(a); };
-            for (int set = 0; set < nsets; set++) {
-                const size_t so = (size_t)set * F64_TABLE_ELEMS2;
-                for (int c = 0; c < 16; c++)
-                    for (int t = 0; t < 64; t++) put6(so + (size_t)c * 64 + t, -PI2 * (double)((c * t) % FFTN) / FFTN);
-                for (int d = 0; d < 4; d++)
-                    for (int t = 0; t < 64; t++) put6(so + (size_t)F64_TAB_D + d * 64 + t, -PI2 * (double)(t * d) / F4K_N);
-            }
-            std::vector<double> cs(F4K_N), sn(F4K_N), Hr(F4K_N), Hi(F4K_N);
-            for (int k = 0; k < F4K_N; k++) { cs[k] = std::cos(-PI2 * k / F4K_N); sn[k] = std::sin(-PI2 * k / F4K_N); }
-            for (int part = 0; part < np; part++) {
-                const unsigned m0 = np == 1 ? 0 : part * 2048u, m1 = np == 1 ? ntaps : (part + 1 < np ? (part + 1) * 2048u : ntaps);
-                const size_t so = (size_t)(part / 2) * F64_TABLE_ELEMS2;
-                const bool second = (part & 1) != 0;
-                for (int k = 0; k < F4K_N; k++) {
-                    double sr = 0, si = 0;
-                    for (unsigned m = m0; m < m1; m++) {
-                        const int a = (int)(((long)k * (m - m0)) % F4K_N);
-                        const double hr = taps_complex ? taps[2 * m] : taps[m], hi = taps_complex ? taps[2 * m + 1] : 0.0;
-                        sr += hr * cs[a] - hi * sn[a];
-                        si += hr * sn[a] + hi * cs[a];
-                    }
-                    Hr[k] = sr / F4K_N;
-                    Hi[k] = si / F4K_N;
-                }
-                for (int r = 0; r < 64; r++)
-                    for (int l = 0; l < 64; l++) {
-                        const int k = 64 * f64_index(r) + l;
-                        const size_t o = so + (size_t)(second ? F64_TAB_H1 : F64_TAB_H) + (size_t)r * 64 + l;
-                        t6[2 * o] = (float)Hr[k];
-                        t6[2 * o + 1] = (float)Hi[k];
-                        if (part == 0 && l <= 32) {
-                            const size_t os = (size_t)F64_TAB_HSYM + (size_t)f64_index(r) * F64_HSYM_ROW + l;
-                            t6[2 * os] = (float)Hr[k];
-                            t6[2 * os + 1] = (float)Hi[k];
-                        }
-                    }
-            }
-            if (upload(q->d_fft64_tables, t6.data(), t6.size() * sizeof(float))) return nullptr;
-            q->fft64_np = np;
-        }
-    }
-    if (q->use_fft) {
-        long N = 1L << (long)std::floor(std::log(8.0 * ntaps) / std::log(2.0));   // firfilter.lua:329
-        q->L = N - (long)ntaps + 1;
-        if (q->pending.reserve((size_t)q->L * q->S * sizeof(float))) return nullptr;
-    }
+    if ((T & FIR_TAB_FFT64_LONG) && up(q->d_fft64_tables, fir_fft64_long_tables(taps, ntaps, taps_complex, p.fft64_np))) return nullptr;
+    if (q->use_fft && q->pending.reserve((size_t)q->L * q->S * sizeof(float))) return nullptr;      // the framing's tail of less than a block
     if (q->reset()) return nullptr;
     return q.release();
 }

@@ -315,6 +315,25 @@ def test_fir_kernel_form_table_on_the_cpu(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
 
 
+def test_fir_plan_and_tables_on_the_cpu(tmp_path):
+    """What fir_build() makes of a request is host arithmetic with two homes: luaradio_amd/csrc/fir_plan.h (fir_resolve(): request -> refusal or shape -
+    the tap-count ranges, the LDS bounds of the Toeplitz tap arrays, the fall-backs) and luaradio_amd/csrc/fir_tables.h (one builder per device table).
+    tools/host_fir_tables_check.hip holds fir_resolve() to a literal table derived by hand from the fir_build() that spelled all of it inline (every
+    refusal and their order, both sides of every range, the requests behind the shapes of host_fir_form_check.hip), and every table to its definition:
+    each H slot, by the kernel's documented index map, a bijection onto the bins and within one Float32 ulp at sum |h| / N of a long-double DFT of
+    asymmetric taps, partition by partition; each twiddle section; the polyphase decimator's branches with and without a rotator."""
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "host_fir_tables_check")
+    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O1", "-std=c++17", "-Wno-unused-function", "-I", os.path.join(ROOT, "luaradio_amd", "csrc"),
+                        "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tools", "host_fir_tables_check.hip")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip().endswith("OK"), r.stdout + r.stderr
+
+
 def test_counted_stage_scratch_layouts_on_the_cpu(tmp_path):
     """The stages with a data-dependent output count carve one scratch buffer into typed lists (luaradio_amd/csrc/stage_counted.h; what they carry between calls: stage_carry.h).  A wrong offset
     or a missed alignment shows only at a tile count where the padding matters, so tools/host_carve_check.hip walks the layouts the stages use

@@ -18,7 +18,8 @@ using namespace lrhip;
 
 typedef FirForm F;
 typedef FirFftForm X;
-// shapes as fir_build() makes them.  ks: fir_mfma_ksteps(M, D, S) = (4 / S - 1 + 15 D + M + 3) / 4 where a Toeplitz table exists, else 0
+// shapes as fir_resolve() (fir_plan.h) makes them of a request: the resolve table of tools/host_fir_tables_check.hip pins the request behind each of the
+// shapes named below to these numbers.  ks: fir_mfma_ksteps(M, D, S) = (4 / S - 1 + 15 D + M + 3) / 4 where a Toeplitz table exists, else 0
 static FirShape shp(int M, int S, unsigned D, int ks) { FirShape s; s.M = M; s.S = S; s.D = D; s.ksteps = ks; return s; }
 static FirShape ctaps(FirShape s, bool table4 = false) { s.taps_complex = 1; s.ctaps4 = table4; return s; }
 static FirShape rot(FirShape s) { s.rot = true; return s; }
